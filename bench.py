@@ -30,16 +30,27 @@ cpu_baseline times the reference's own CPU path (oracle/_ref) on a bounded
 sample of the same batch, on the host cores this process may use and on one
 thread as the reference builds it.
 
-Beside `value` (never in it), a one-GPU default run also times: the `wterm`
-batch; the bit-exact order-preserving kernels (`sequential`, with their own
-issue-model roofline, and `sequential.configs2`: configs[2] at NR_TIMESLOTS=4
-with the order-preserving gridder); and BASELINE configs[2] (`configs2`, C =
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the line: `value`, `ms_per_step`, the per-kernel times from
+the timed steps' own events and the rooflines priced from them.  Everything
+else below runs only with `--full`: the pipeline steps, the energy counter,
+`weak_scaling`, `reference_hip_mi355x`, the side legs and `cpu_baseline`
+(null in a plain line).  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/subgrids.npy and DIR/visibilities.npy (float32; a fixed,
+seeded sample of whole subgrids and visibility blocks, at most 48 MiB), so
+that two builds can be compared output for output on the same inputs.
+
+Beside `value` (never in it), a one-GPU default `--full` run also times: the
+`wterm` batch; the bit-exact order-preserving kernels (`sequential`, with
+their own issue-model roofline, and `sequential.configs2`: configs[2] at
+NR_TIMESLOTS=4 with the order-preserving gridder); and BASELINE configs[2] (`configs2`, C =
 256 at NR_TIMESLOTS=4) and configs[4] (`configs4`, S = 64, the full batch) on
 the default kernels, each with its roofline, counter traffic and issue
 efficiency priced from the committed profile of the same launch
 (profiles/traffic.json).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload default]
+    python bench.py [--gpus N --steps K --warmup W] [--full]
+                    [--dump-outputs DIR] [--workload default]
                     [--mode sharded|replicated] [--dump DIR]
 
 `--gpus N` with N > 1 works both under torchrun (one rank per GPU, RANK /
@@ -163,6 +174,20 @@ def parse(argv=None):
                     help="rank 0 writes the gathered gridder subgrids, "
                          "degridded visibilities and summed uv grid here "
                          "(.npy; tests/test_gpu_dist.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything the line carries beside "
+                         "`value`: the pipeline steps, the energy counter, "
+                         "the weak-scaling figure, the side legs, the "
+                         "reference HIP comparison and the CPU baseline "
+                         "(the --no-* options then skip single ones); "
+                         "without it only the timed steps run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one "
+                         "computed (gridder subgrids, degridded "
+                         "visibilities) as DIR/<name>.npy, float32; a "
+                         "fixed, seeded sample of whole subgrids and "
+                         "visibility blocks where the output is larger "
+                         "than the budget (sample_outputs)")
     ap.add_argument("--traffic-file", default=os.path.join(
         REPO, "profiles", "traffic.json"))
     ap.add_argument("--plan-only", action="store_true",
@@ -1111,8 +1136,10 @@ def main(argv=None):
     stream = torch.cuda.current_stream()
     progress("timing")
 
-    from idg_amd.energy import EnergyMeter
-    meter = EnergyMeter(local_rank)
+    meter = None
+    if args.full:
+        from idg_amd.energy import EnergyMeter
+        meter = EnergyMeter(local_rank)
     warm = {}
     elapsed_max, t_grid, t_degrid, joules, elapsed, outs = time_steps(
         w, dev, nsub, args.steps, args.warmup, stream, dist, meter,
@@ -1161,9 +1188,15 @@ def main(argv=None):
         roofline_hbm["counter_gbs"] = round(roofline["traffic"] / t_dom / 1e9,
                                             2)
 
-    # ---- pipeline steps around the path (not in `value`) ----------------
+    # ---- what the last timed step computed (--dump-outputs) --------------
+    dumped = None
+    if args.dump_outputs:
+        dumped = sample_outputs(args.dump_outputs, outs, T, rank, world)
+
+    # ---- pipeline steps around the path (not in `value`; --full, and for
+    # --dump's uv grid) ----------------------------------------------------
     pipeline, grid_sum = None, None
-    if not args.no_pipeline or args.dump:
+    if (args.full and not args.no_pipeline) or args.dump:
         progress("pipeline steps")
         pipeline, grid_sum = time_pipeline(w, dev, outs[0], stream,
                                            args.steps, world, dist)
@@ -1203,7 +1236,8 @@ def main(argv=None):
 
     # ---- the other scaling mode, beside the headline ----------------------
     weak = None
-    if world > 1 and args.mode == "sharded" and not args.no_weak:
+    if (args.full and world > 1 and args.mode == "sharded" and
+            not args.no_weak):
         del dev, outs
         torch.cuda.empty_cache()
         full = upload(shard_batch(a, rank, world, "replicated"))
@@ -1224,8 +1258,8 @@ def main(argv=None):
 
     # ---- the wterm batch and the sequential kernels, beside `value` -------
     side = None
-    if (world == 1 and args.workload == "default" and not args.no_side and
-            not args.dump):
+    if (args.full and world == 1 and args.workload == "default" and
+            not args.no_side and not args.dump):
         progress("side legs (wterm batch, sequential kernels, configs[2] "
                  "and configs[4])")
         side = time_side_legs(args, w, a, dev, nsub, stream, dist,
@@ -1279,15 +1313,17 @@ def main(argv=None):
         "energy": energy,
         "reference_hip_mi355x": (reference_hip_for(
             args.workload, sec_per_step, t_grid, t_degrid)
-            if world == 1 else None),
+            if args.full and world == 1 else None),
         "wterm": side["wterm"] if side else None,
         "sequential": side["sequential"] if side else None,
         "configs2": side.get("configs2") if side else None,
         "configs4": side.get("configs4") if side else None,
         "cpu_baseline": None,
+        "full": args.full,
+        "dump_outputs": dumped,
     }
     t_cpu = 0.0
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("cpu baseline")
         t_c0 = time.perf_counter()
         result["cpu_baseline"] = cpu_baseline(w, a, args.cpu_sample_subgrids)
@@ -1335,6 +1371,53 @@ def dump_outputs(path, a, part, outs, grid_sum, rank, world, mode, dist):
             np.save(os.path.join(path, "grid.npy"), grid_sum.cpu().numpy())
         with open(os.path.join(path, "meta.json"), "w") as f:
             json.dump({"world": world, "mode": mode, "counts": counts}, f)
+
+
+DUMP_BUDGET = 24 << 20      # bytes per --dump-outputs array (two arrays)
+
+
+def sample_rows(n, row_bytes, seed):
+    """Which of an output's n rows --dump-outputs keeps: all of them where
+    they fit DUMP_BUDGET, else a sorted draw without replacement from a
+    generator seeded with `seed` (the same rows on every run)."""
+    import numpy as np
+    keep = min(n, DUMP_BUDGET // max(1, row_bytes))
+    if keep >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+
+
+def sample_outputs(path, outs, T, rank, world):
+    """--dump-outputs: the two arrays the last timed step left on the device
+    -- the gridder's subgrids [n][4][S][S] complex and the degridder's
+    visibilities, as blocks of T rows [n][T][C][4] complex -- written as
+    float32 .npy (the trailing axis is re/im).  Whole subgrids and whole
+    T-row blocks are kept, every one where the array fits DUMP_BUDGET, else
+    the seeded sample of sample_rows.  With more than one rank each writes
+    its own shard's, ranks above 0 as <name>.rank<r>.npy.  Returns the
+    description the result line carries."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sub = outs[0]
+    vis = outs[1][:outs[1].shape[0] // T * T]
+    vis = vis.reshape(-1, T, *vis.shape[1:])
+    info = {"dir": path, "dtype": "float32", "arrays": {}}
+    for seed, (name, t) in enumerate((("subgrids", sub),
+                                      ("visibilities", vis))):
+        n = t.shape[0]
+        rows = sample_rows(n, t[0].numel() * 4 if n else 1, seed)
+        kept = t[torch.from_numpy(rows).to(t.device)].float().cpu().numpy()
+        fname = name + (f".rank{rank}" if rank else "") + ".npy"
+        np.save(os.path.join(path, fname), kept)
+        info["arrays"][name] = {
+            "shape": list(kept.shape), "of": n,
+            "rows": ("all" if len(rows) == n else
+                     f"numpy default_rng({seed}).choice({n}, {len(rows)}, "
+                     "replace=False), sorted")}
+    if world > 1:
+        info["ranks"] = "each rank writes its own shard's arrays"
+    return info
 
 
 def reference_hip_for(workload_name, sec_per_step, t_grid, t_degrid):

@@ -276,6 +276,49 @@ def test_extra_warmup_steps():
     assert bench.extra_warmup_steps(0.002, 0.0) == 0    # exactly W steps
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+    # bench.py --dump-outputs on host tensors: whole subgrids / T-row blocks,
+    # every one where the array fits, else the same seeded rows on every call
+    import bench
+    import torch
+    T = 4
+    sub = torch.arange(5 * 4 * 8 * 8 * 2, dtype=torch.float32).reshape(
+        5, 4, 8, 8, 2)
+    vis = torch.arange(5 * T * 3 * 4 * 2, dtype=torch.float32).reshape(
+        5 * T, 3, 4, 2)
+    info = bench.sample_outputs(str(tmp_path), (sub, vis), T, 0, 1)
+    got = {n: np.load(tmp_path / (n + ".npy"))
+           for n in ("subgrids", "visibilities")}
+    assert all(g.dtype == np.float32 for g in got.values())
+    assert np.array_equal(got["subgrids"], sub.numpy())
+    assert np.array_equal(got["visibilities"],
+                          vis.numpy().reshape(5, T, 3, 4, 2))
+    assert info["arrays"]["subgrids"]["rows"] == "all"
+    # a budget of two subgrids: two of the five, sorted, the same every time
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * sub[0].numel() * 4)
+    rows = bench.sample_rows(5, sub[0].numel() * 4, 0)
+    assert len(rows) == 2 and rows[0] < rows[1]
+    assert np.array_equal(rows, bench.sample_rows(5, sub[0].numel() * 4, 0))
+    info = bench.sample_outputs(str(tmp_path), (sub, vis), T, 1, 2)
+    assert np.array_equal(np.load(tmp_path / "subgrids.rank1.npy"),
+                          sub.numpy()[rows])
+    assert info["arrays"]["subgrids"]["shape"] == [2, 4, 8, 8, 2]
+    # configs[1]: 24 MiB per array, 50.3 MB in all
+    monkeypatch.undo()
+    n_sub = len(bench.sample_rows(24500, 4 * 32 * 32 * 8, 0))
+    n_vis = len(bench.sample_rows(24500, 128 * 16 * 4 * 8, 1))
+    assert (n_sub, n_vis) == (768, 384)
+    assert n_sub * 4 * 32 * 32 * 8 + n_vis * 128 * 16 * 4 * 8 <= 64e6
+
+
 @pytest.mark.timeout(120)
 def test_gloo_world2_warmup_count_agreed(tmp_path):
     mp.start_processes(_warmup_worker, args=(2, _free_port(), str(tmp_path)),

@@ -77,6 +77,44 @@ def test_bench_two_ranks_sharded_equals_one_rank(tmp_path, launcher):
     assert np.abs(g2 - g1).max() <= 1e-6 * np.abs(g1).max()
 
 
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_its_last_step_outputs(tmp_path):
+    """A plain run (no --full) times only the steps: everything beside
+    `value` is null.  --dump-outputs writes the seeded sample of what the
+    last timed step computed: the same arrays on a second run with another
+    step count, and exactly those rows of the whole outputs (--dump)."""
+    import bench
+    common = ["--gpus", "1", "--warmup", "1", "--timeslots", "2",
+              "--min-warmup-s", "0"]
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    a = _run([sys.executable, "bench.py", "--steps", "2", "--dump-outputs",
+              str(tmp_path / "a")] + common, env)
+    b = _run([sys.executable, "bench.py", "--steps", "3", "--dump-outputs",
+              str(tmp_path / "b"), "--dump", str(tmp_path / "whole")] + common,
+             env)
+    assert (a["steps"], b["steps"]) == (2, 3) and a["full"] is False
+    assert a["value"] > 0 and a["ms_per_step"] > 0
+    assert abs(a["value"] * a["ms_per_step"] * 1e3 /
+               a["config"]["visibilities_per_step"] - 1) < 1e-3
+    for k in ("pipeline", "energy", "weak_scaling", "reference_hip_mi355x",
+              "wterm", "sequential", "configs2", "configs4", "cpu_baseline"):
+        assert a[k] is None, k
+    total = 0
+    for seed, name in enumerate(("subgrids", "visibilities")):
+        x = np.load(tmp_path / "a" / (name + ".npy"))
+        y = np.load(tmp_path / "b" / (name + ".npy"))
+        whole = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, y), name
+        rows = bench.sample_rows(whole.shape[0], whole[0].nbytes, seed)
+        assert 0 < len(rows) < whole.shape[0] == 2450
+        assert np.array_equal(x, whole[rows]), name
+        assert np.abs(x).max() > 0
+        assert a["dump_outputs"]["arrays"][name]["shape"] == list(x.shape)
+        total += x.nbytes
+    assert total <= 64e6
+
+
 @pytest.mark.timeout(600)
 def test_bench_collectives_over_rccl_single_rank(tmp_path):
     """The RCCL side of the same path on the box's one device: bench.py runs

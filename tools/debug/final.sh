@@ -11,6 +11,6 @@ mkdir -p $out
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 \
   --timeout-method thread > $out/pytest_gpu.txt 2>&1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1
-timeout -k 10 400 python bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err
 bash tools/probes/profile_all.sh "$tag"
 echo final done

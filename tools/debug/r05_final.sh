@@ -14,7 +14,7 @@ if [ "$part" = 1 ]; then
   timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 300 \
     --timeout-method thread > $out/pytest_gpu.txt 2>&1
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1
-  timeout -k 10 400 python bench.py > $out/bench.json 2> $out/bench.err
+  timeout -k 10 400 python bench.py --full > $out/bench.json 2> $out/bench.err
 else
   timeout -k 10 400 bash tools/probes/profile_round.sh r05 > $out/prof.log 2>&1
   timeout -k 10 500 bash tools/probes/pmc_sq.sh r05 > $out/pmc.log 2>&1

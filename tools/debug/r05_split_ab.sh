@@ -14,7 +14,7 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
 for wl in default s64; do
   for rep in 1 2; do
     for form in 1 rows; do
-      IDG_SPLIT_FFT=$form timeout -k 10 200 python bench.py --workload $wl --no-cpu-baseline --no-side \
+      IDG_SPLIT_FFT=$form timeout -k 10 200 python bench.py --full --workload $wl --no-cpu-baseline --no-side \
         --steps 5 > $out/${wl}_${form}_$rep.json 2> $out/${wl}_${form}_$rep.err
       python -c "
 import json; p=json.load(open('$out/${wl}_${form}_$rep.json'))['pipeline']
@@ -22,11 +22,12 @@ print('$wl', '$form', $rep, 'splitter_fft', p['splitter_fft_ms'], 'splitter', p[
     done
   done
 done
+repo=$PWD
 cd /tmp && export TMPDIR=/tmp
 for wl in default s64; do
   for form in 1 rows; do
     IDG_SPLIT_FFT=$form timeout -s KILL 200 rocprofv3 --kernel-trace -d $GRAFT_REPO_ROOT/$out/kt_${wl}_$form -o run -- \
-      python3 $GRAFT_REPO_ROOT/bench.py --workload $wl --no-cpu-baseline --no-side --steps 3 --warmup 1 \
+      python3 $repo/bench.py --full --workload $wl --no-cpu-baseline --no-side --steps 3 --warmup 1 \
       > /dev/null 2> $GRAFT_REPO_ROOT/$out/kt_${wl}_$form.err
   done
 done

@@ -13,6 +13,6 @@ for lib in "$@"; do
   IDG_MI355X_LIB=$GRAFT_REPO_ROOT/$lib timeout -k 10 300 rocprofv3 --kernel-trace \
     --output-format csv -d "$out/kt_$n" -o run -- \
     python3 "$GRAFT_REPO_ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline \
-    --no-side > "$out/bench_$n.json"
+    --no-side --full > "$out/bench_$n.json"
 done
 echo "r06_adder_kt done"

@@ -13,5 +13,5 @@ if [ "${2:-}" != "skip-tests" ]; then
     --timeout-method thread > $out/pytest_gpu.txt 2>&1
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1
 fi
-timeout -k 10 600 python bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err
 echo "r06_suite $tag done"

@@ -9,7 +9,8 @@
 #   suite[=K]            GPU test suite (pytest -m gpu), optional -k filter K
 #   suite@LIB[=K]        the same on another library build (IDG_MI355X_LIB)
 #   smoke                __graft_entry__.smoke()
-#   bench[=ARGS]         one bench.py line (ARGS with ',' for ' ')
+#   bench[=ARGS]         one bench.py line (ARGS with ',' for ' '; --full
+#                        for the pipeline, side legs and CPU baseline)
 #   ab=A.so,B.so,...     kernel A/B, interleaved, two reps (ab.sh; STEPS,
 #                        BENCH_ARGS from the environment)
 #   abpipe=A.so,B.so     pipeline-kernel A/B (ab_pipe.sh)
