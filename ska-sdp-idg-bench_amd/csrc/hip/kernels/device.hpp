@@ -73,7 +73,8 @@ __device__ __forceinline__ floatx2 tail_k_rev(floatx2 neg_pidx, float kb) {
 // sums over channels, so the +3c / -c pattern cancels in every coherent sum
 // to first order (tests/emul/tail_mean_emul.py); kPrecFlush
 // (gridder, S = 32) sums the accumulator tiles into an f32 master every
-// kFlushFills fills (at most 32 K-steps each).
+// kFlushFills fills of at most 32 K-steps each (the mirror path's fills hold
+// 64: every kFlushFills / 2 of them, the same K-steps).
 constexpr int kPrecTail = 1, kPrecFlush = 2, kPrecTailAlt = 4;
 // Every 16 fills (round 5; 8 in round 4): C = 256 gridder 3.35e-6 from the
 // exact sum against 2.74e-6 (the reference's own output: 1.27e-5), its

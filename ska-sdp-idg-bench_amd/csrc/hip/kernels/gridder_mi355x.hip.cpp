@@ -236,6 +236,14 @@ __device__ __forceinline__ void pixel_geometry(int p, int S, float image_size,
 // with Bc = (V.re | V.im) and Bs = (-V.im | V.re) per correlation.  X and Y
 // are two dense GEMMs per 16-pixel tile (v_mfma_f32_16x16x32_f16):
 //   X[pixel][col] += sum_k Ac[pixel][k] * Bc[k][col]      (Y likewise)
+// Bs is Bc with the re/im columns of each correlation swapped and one sign
+// flipped, and X and Y stay in separate tiles until the epilogue, so only Bc
+// is built: the sin GEMM accumulates Y' = s * Bc and the epilogue takes
+// Y.re = -Y'.im, Y.im = Y'.re.  Negation is exact through the scale, the f16
+// split and every product, but the MFMA's internal sum is not sign-symmetric
+// (DESIGN.md §3.1), so Y equals s * Bs only up to the MFMA's internal
+// rounding: last-bit differences.  The runtime-S kernels
+// keep both fragments.
 // K = 16 items (4 timesteps x 4 channels) x {hi, lo} of the f16-split phasor
 // component; B columns = 8 components [hi | lo] of the f16-split visibility.
 // Lane l = (group g = l/16, pixel/column l%16): group g takes timestep 4q+g of
@@ -250,6 +258,24 @@ __device__ __forceinline__ void pixel_geometry(int p, int S, float image_size,
 #define IDG_GRID_KSBUF 32
 #endif
 constexpr int kKsBuf = IDG_GRID_KSBUF;  // K-steps (16 items each) of B fragments per fill
+// The mirror path keeps one fragment per (K-step, lane), not two (grid_mfma:
+// its sin GEMM runs against the cos GEMM's fragment and the epilogue maps
+// the columns), so the same LDS holds twice the K-steps per fill.
+#ifndef IDG_GRID_KSBUF_MIRROR
+#define IDG_GRID_KSBUF_MIRROR (2 * IDG_GRID_KSBUF)
+#endif
+constexpr int kKsBufMirror = IDG_GRID_KSBUF_MIRROR;
+// K-steps of the mirror fill whose loads a wave issues before it splits the
+// first (4 loads per K-step and lane)
+#ifndef IDG_GRID_FILL_DEPTH
+#define IDG_GRID_FILL_DEPTH 2
+#endif
+// One K-step at a time where the window's registers would be spilled: the
+// combined kernels off S = 32, whose general path holds its pixel geometry
+// in VGPRs.
+constexpr int mirror_fill_depth(int S_CT, bool combined) {
+  return combined && S_CT != 32 ? 1 : IDG_GRID_FILL_DEPTH;
+}
 
 // NW waves per workgroup, AT 16 x 16 accumulator tiles per wave (mirror
 // path: X and Y of PT pixel tiles, AT = 2 PT; general path: one fused X + Y
@@ -257,7 +283,10 @@ constexpr int kKsBuf = IDG_GRID_KSBUF;  // K-steps (16 items each) of B fragment
 template <int AT, int NW>
 struct MfmaLds {
   static constexpr int kObufFloats = NW * 16 * AT * 16;  // accumulator tiles
-  static constexpr int kBbufWords = kKsBuf * 64 * 8;  // uint4 X + uint4 Y
+  // general: uint4 X + uint4 Y per (K-step, lane); mirror: one uint4 for
+  // twice the K-steps
+  static constexpr int kBbufWords = kKsBuf * 64 * 8;
+  static_assert(kKsBufMirror * 64 * 4 <= kBbufWords, "one buffer, two layouts");
   // uvw of the fill's timesteps (at most 4 * kKsBuf), float4 each
   static constexpr int kUvwOff =
       kObufFloats > kBbufWords ? kObufFloats : kBbufWords;
@@ -316,7 +345,8 @@ __device__ __forceinline__ void l2_prefetch_dma(const void *src,
 // the subgrid's own output slot (32 KB at S = 32, one pass), which only the
 // epilogue writes, after the master is read back.
 template <int S_CT, int PT, int CB, int NW, bool MIRROR, bool FFT = false,
-          int PREC = kPrecTail, bool PRESCAN = false, bool OPAQUE_TID = !MIRROR>
+          int PREC = kPrecTail, bool PRESCAN = false, bool OPAQUE_TID = !MIRROR,
+          int FILL_D = IDG_GRID_FILL_DEPTH>
 __device__ __forceinline__ void grid_mfma(
     const SubgridSetup &g, int S, int npix, float image_size, int C,
     int nr_stations, const idg::UVWCoordinate<float> *__restrict__ uvw,
@@ -358,8 +388,17 @@ __device__ __forceinline__ void grid_mfma(
   const int nt = g.nr_timesteps;
   const int nchq = (C + 3) / 4;  // channel quads
   const int nquads = (nt + 3) / 4;
-  const int quads_per_fill = nchq <= kKsBuf ? kKsBuf / nchq : 1;
-  const int cq_per_fill = nchq <= kKsBuf ? nchq : kKsBuf;
+  // K-steps of B fragments per fill: the mirror path stores one fragment
+  // per (K-step, lane) and fills twice the K-steps (at most 4 * kKsBuf
+  // timesteps, which is what the uvw area holds)
+  // One fragment on the mirror path of the kernels built for a subgrid
+  // size (S = 32, 64).  The runtime-S kernels keep [X, Y] fragments on both
+  // paths: they have no registers to spare (they spill already), and the
+  // one-fragment fill cost them 8-44 B/lane more scratch.
+  constexpr bool kOneFrag = MIRROR && S_CT != 0;
+  constexpr int KS = kOneFrag ? kKsBufMirror : kKsBuf;
+  const int quads_per_fill = nchq <= KS ? min(KS / nchq, kKsBuf) : 1;
+  const int cq_per_fill = nchq <= KS ? nchq : KS;
   unsigned *slots = lds + Lds::kSlotOff;
 
   // A power-of-two scale 2^-e keeps the visibilities inside f16 range.  It
@@ -370,7 +409,10 @@ __device__ __forceinline__ void grid_mfma(
   // yet set, is split again with the new scale after the f32 sums so far
   // are rescaled by the exact power of two.  Each input byte is thus read
   // once per fill (the first fill's rows twice, back to back, from L2).
-  // PRESCAN: the caller scanned them already (prologue_scan: vmax_pre).
+  // PRESCAN: the caller scanned them already (prologue_scan: vmax_pre; the
+  // rows of the first kKsBuf K-steps on either path, so half of the mirror
+  // path's first fill, whose other half is held to the range like any later
+  // fill).
   float vmax = vmax_pre;
   if (tid < 2) slots[tid] = 0u;
   if constexpr (!PRESCAN) {
@@ -404,7 +446,8 @@ __device__ __forceinline__ void grid_mfma(
 
   const float2 *__restrict__ vsub = visibilities + g.time_offset * C * 4;
 
-  uint4 *bbuf = reinterpret_cast<uint4 *>(lds);  // [ks][64][X, Y]
+  // general: [ks][64][X, Y]; mirror: [ks][64]
+  uint4 *bbuf = reinterpret_cast<uint4 *>(lds);
   float *obuf = reinterpret_cast<float *>(lds);
   float4 *tuvw = reinterpret_cast<float4 *>(lds + Lds::kUvwOff);
 
@@ -520,10 +563,75 @@ __device__ __forceinline__ void grid_mfma(
 #ifdef IDG_DEBUG_SKIPFILL
           // timing experiment only (wrong output): every fill after the
           // first reuses its B fragments
-          for (int ks = fidx > 0 ? nks : wv; ks < nks; ks += NW) {
+          const int ks_first = fidx > 0 ? nks : wv;
 #else
-          for (int ks = wv; ks < nks; ks += NW) {
+          const int ks_first = wv;
 #endif
+          if constexpr (kOneFrag) {
+            // One fragment per (K-step, lane), Bc: the sin GEMM multiplies
+            // it too and the epilogue maps Y' = s * Bc to Y = s * Bs.  Four
+            // loads per K-step, so two K-steps' loads are issued before the
+            // first is split (one L2 round trip per pair).
+            auto load4 = [&](int q_, int j_, float (&b)[4]) {
+              const int c0 = 4 * (j0 + j_);
+              if (full) {
+                const char *blk = reinterpret_cast<const char *>(
+                    vsubf + ((q0 + q_) * 4 * C + c0) * 8);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+#if IDG_GRID_NT_FILL
+                  const __amdgpu_buffer_rsrc_t rsrc =
+                      __builtin_amdgcn_make_buffer_rsrc(
+                          const_cast<char *>(blk), static_cast<short>(0),
+                          0x7ffffff0, 0x00020000);
+                  b[u] = __builtin_bit_cast(
+                      float, __builtin_amdgcn_raw_buffer_load_b32(
+                                 rsrc, static_cast<int>(off_c), 32 * u, 2));
+#else
+                  b[u] = *reinterpret_cast<const float *>(blk + off_c + 32 * u);
+#endif
+                }
+              } else {
+                const int t = (q0 + q_) * 4 + grp;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                  const bool ok = t < nt && c0 + u < C;
+                  b[u] = ok ? vsubf[(t * C + c0 + u) * 8 + w_c] : 0.0f;
+                }
+              }
+            };
+            auto put = [&](int ks, const float (&b)[4]) {
+              lmax = fmaxf(lmax, fmaxf(fmaxf(fabsf(b[0]), fabsf(b[1])),
+                                       fmaxf(fabsf(b[2]), fabsf(b[3]))));
+              const unsigned xc =
+                  split_part(b[0] * scale, b[1] * scale, bpart);
+              const unsigned yc =
+                  split_part(b[2] * scale, b[3] * scale, bpart);
+              bbuf[ks * 64 + lane] = make_uint4(xc, xc, yc, yc);
+            };
+            auto advance = [&]() {
+              jj += NW;
+              while (jj >= nj) {
+                jj -= nj;
+                ++qq;
+              }
+            };
+            constexpr int D = FILL_D;
+            for (int ks = ks_first; ks < nks; ks += D * NW) {
+              float b[D][4];
+#pragma unroll
+              for (int d = 0; d < D; ++d)
+                if (ks + d * NW < nks) {  // wave-uniform
+                  load4(qq, jj, b[d]);
+                  advance();
+                }
+#pragma unroll
+              for (int d = 0; d < D; ++d)
+                if (ks + d * NW < nks) put(ks + d * NW, b[d]);
+            }
+          } else {
+          // general path: [X, Y] fragments, Bc and Bs
+          for (int ks = ks_first; ks < nks; ks += NW) {
             const int t = (q0 + qq) * 4 + grp;
             const int c0 = 4 * (j0 + jj);
             float bc[4], bs[4];
@@ -579,6 +687,7 @@ __device__ __forceinline__ void grid_mfma(
             const unsigned ys = split_part(bs[2], bs[3], bpart);
             bbuf[(ks * 64 + lane) * 2] = make_uint4(xc, xc, yc, yc);
             bbuf[(ks * 64 + lane) * 2 + 1] = make_uint4(xs, xs, ys, ys);
+          }
           }
           // wave max (rows of 16 by DPP, then the four row maxima), one LDS
           // atomic per wave (an atomicMax from every lane would be expanded
@@ -751,8 +860,10 @@ __device__ __forceinline__ void grid_mfma(
               const int jj = jb + u;
               if (jj >= je) break;
               const int ks = qq * nj + jj;
-              const uint4 bx = bbuf[(ks * 64 + lane) * 2];
-              const uint4 by = bbuf[(ks * 64 + lane) * 2 + 1];
+              // mirror: both GEMMs read the one fragment (Y' = s * Bc)
+              const int fr = ks * 64 + lane;
+              const uint4 bx = bbuf[kOneFrag ? fr : 2 * fr];
+              const uint4 by = kOneFrag ? bx : bbuf[2 * fr + 1];
               const half8 bfx = pack4(bx.x, bx.y, bx.z, bx.w);
               const half8 bfy = pack4(by.x, by.y, by.z, by.w);
 #pragma unroll
@@ -795,10 +906,15 @@ __device__ __forceinline__ void grid_mfma(
           }
         }
         if constexpr (kFlush) {
-          // every kFlushFills fills except the last (wave-uniform)
+          // every kFlushFills * kKsBuf K-steps' worth of fills (so both
+          // paths flush after the same K-steps) except the last
+          // (wave-uniform)
+          constexpr int kFlushEvery = kFlushFills * kKsBuf / KS;
+          static_assert(kFlushEvery * KS == kFlushFills * kKsBuf,
+                        "the flush period is a whole number of fills");
           const bool last =
               j0 + cq_per_fill >= nchq && q0 + quads_per_fill >= nquads;
-          if (!last && (fidx + 1) % kFlushFills == 0) {
+          if (!last && (fidx + 1) % kFlushEvery == 0) {
             const float unsc = ldexpf(1.0f, e - kBS);
 #pragma unroll
             for (int i = 0; i < PT; ++i) flush_tile(accx[i], i, unsc);
@@ -872,8 +988,19 @@ __device__ __forceinline__ void grid_mfma(
         const float yv[8] = {yh0.x + yl0.x, yh0.y + yl0.y, yh0.z + yl0.z,
                              yh0.w + yl0.w, yh1.x + yl1.x, yh1.y + yl1.y,
                              yh1.z + yl1.z, yh1.w + yl1.w};
+        if constexpr (kOneFrag) {
+          // the tiles hold Y' = s * Bc; Bs is Bc with each correlation's
+          // re/im columns swapped and one sign flipped: Y.re = -Y'.im,
+          // Y.im = Y'.re (equal to s * Bs up to the MFMA's internal rounding)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] = yv[j];
+          for (int k = 0; k < 4; ++k) {
+            y[2 * k] = -yv[2 * k + 1];
+            y[2 * k + 1] = yv[2 * k];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) y[j] = yv[j];
+        }
       }
       // the phase tail of the reduction: base pixel * exp(i poff eps),
       // mirror pixel (phase_offset -poff) * exp(-i poff eps)
@@ -950,7 +1077,9 @@ __device__ __forceinline__ bool prologue_scan(
   bool w_nonzero = false;
   for (int t = tid; t < g.nr_timesteps; t += NW * 64)
     w_nonzero |= uvw[g.time_offset + t].w != 0.0f;
-  // grid_mfma's first fill: quads_per_fill timestep quads, all channels
+  // the first kKsBuf K-steps of grid_mfma on either path (the general
+  // path's first fill, half of the mirror path's): quads_per_fill timestep
+  // quads, all channels
   const int nchq = (C + 3) / 4;
   const int quads_per_fill = nchq <= kKsBuf ? kKsBuf / nchq : 1;
   const float4 *v4 = reinterpret_cast<const float4 *>(
@@ -1032,7 +1161,8 @@ __global__ void __launch_bounds__(MODE == 1 ? 64 * IDG_GRID_NW : kBlock,
         S % 2 == 0 && g.w_offset == 0.0f;
     const float vmax = prologue_max<NW>(red);
     if (mirror)
-      grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true>(
+      grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true, false,
+                mirror_fill_depth(S_CT, true)>(
           g, S, npix, image_size, C, nr_stations, uvw, wavenumbers,
           visibilities, spheroidal, aterms, out, lds, vmax);
     else
@@ -1194,7 +1324,8 @@ __global__ void __launch_bounds__(64 * IDG_GRID_NW, IDG_GRID_WAVES)
   static_assert(SPLIT == 1 || (S_CT > 0 && SPLIT * kPass >= S_CT * S_CT / 2 &&
                                (SPLIT - 1) * kPass < S_CT * S_CT / 2),
                 "mirror_split(S) does not match the pass size");
-  grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true>(
+  grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true, false,
+            mirror_fill_depth(S_CT, false)>(
       g, S, npix, image_size, nr_channels, nr_stations, uvw, wavenumbers,
       visibilities, spheroidal, aterms,
       subgrids + static_cast<size_t>(s) * 4 * npix, lds,
