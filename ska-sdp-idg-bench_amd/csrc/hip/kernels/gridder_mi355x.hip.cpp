@@ -1517,10 +1517,13 @@ GridderSet gridder_set_for(int prec) {
 
 // IDG_GRIDDER_IMPL=valu selects the VALU mirror path (A/B comparisons);
 // IDG_GRIDDER_IMPL=sequential the order-preserving kernel, bit-exact to the
-// reference's CPU output (sequential_mi355x.hip.cpp).
+// reference's CPU output (sequential_mi355x.hip.cpp); IDG_GRIDDER_IMPL=
+// ordered the reference's summation order with the hardware sin / cos
+// (ordered_mi355x.hip.cpp).
 static int gridder_impl() {
   const char *v = std::getenv("IDG_GRIDDER_IMPL");
   if (v && std::string(v) == "sequential") return 2;
+  if (v && std::string(v) == "ordered") return 3;
   return (v && std::string(v) == "valu") ? 0 : 1;
 }
 
@@ -1534,6 +1537,14 @@ KernelChoice select_gridder(const Problem &p) {
              : p.subgrid_size == 64 ? "gridder_sequential_mi355x_s64"
                                     : "gridder_sequential_mi355x_generic";
     return k;  // no FFT epilogue: launch() runs launch_subgrid_fft after it
+  }
+  if (gridder_impl() == 3) {  // one combined launch, k.prec = 0, no epilogue
+    k.func = ordered_gridder(p.subgrid_size);
+    k.block = ordered_block();
+    k.name = p.subgrid_size == 32   ? "gridder_ordered_mi355x_s32"
+             : p.subgrid_size == 64 ? "gridder_ordered_mi355x_s64"
+                                    : "gridder_ordered_mi355x_generic";
+    return k;
   }
   const bool mfma = gridder_impl() == 1;
   k.block = mfma ? 64 * IDG_GRID_NW : kBlock;

@@ -215,6 +215,13 @@ const void *sequential_gridder(int subgrid_size);
 const void *sequential_degridder(int subgrid_size);
 int sequential_block();
 
+// The ordered gridder (kernels/ordered_mi355x.hip.cpp): the reference's
+// summation order and product forms with the hardware sin / cos of the MFMA
+// kernels -- within the reference's 1e-5 bar at any T x C, not bit-exact;
+// same ABI and launch shape.  Selected per call by IDG_GRIDDER_IMPL=ordered.
+const void *ordered_gridder(int subgrid_size);
+int ordered_block();
+
 // Returns an empty string if every subgrid's time range, stations and A-term
 // slot lie inside the buffers, else a description of the first violation.
 std::string validate(const Problem &p, const Extents &e,
