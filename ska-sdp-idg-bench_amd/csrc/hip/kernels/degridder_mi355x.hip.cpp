@@ -48,16 +48,6 @@
 #ifndef IDG_DEGRID_WAVES
 #define IDG_DEGRID_WAVES 4
 #endif
-// A subgrid of several K-chunks (S = 64; the general path of the combined
-// kernel) takes its f16 scale per chunk, from the chunk's own entries, as a
-// single-chunk subgrid does (round 5).  IDG_DEGRID_CHUNK_SCALE=0: one scale
-// per subgrid from a pass over every pixel entry before the first chunk --
-// whose bytes the later chunks then re-read from beyond L2 (configs[4]
-// degridder 29.43 -> 29.0 ms, 11.86 -> 10.08 GB per launch; DESIGN.md
-// §5.000).
-#ifndef IDG_DEGRID_CHUNK_SCALE
-#define IDG_DEGRID_CHUNK_SCALE 1
-#endif
 
 namespace idg_mi355x {
 
@@ -209,11 +199,14 @@ static_assert(kInv2PiHi == 0.15915494f, "phase_rev_bcast's inline constant");
 
 // KS: K split -- the workgroup's waves form KS groups of NW / KS waves;
 // every group covers all timesteps and channel tiles, each over its own
-// share of the chunk's K-steps (KS = 2: the 16-wave S = 64 mirror kernel,
-// whose eight timestep waves would otherwise leave half the workgroup idle
-// at T = 128).  Group 1 stores its partial sums, the workgroup barrier
-// orders them (same CU: one L1), group 0 adds its own on top: p1 + p0, the
-// same float as the two-chunk form's p0 + p1 (two-term addition commutes).
+// share of the chunk's K-steps.  Group 1 stores its partial sums, the
+// workgroup barrier orders them (same CU: one L1), group 0 adds its own on
+// top.  Every kernel is built with KS = 1 (the KS = 2 kernel, a 16-wave
+// single-chunk S = 64 mirror kernel, was measured slower and removed;
+// DESIGN.md §5).  The parameter itself stays for now: the compiler does not
+// fold wave % NW and wave / NW, so taking them out changes the instructions
+// and the register allocation of every MFMA degridder kernel, which is a
+// change to measure on its own.
 template <int S_CT, int CT, int CB, int KP, bool MIRROR, int NW,
           bool TAIL = true, int KS = 1>
 __device__ __forceinline__ void degrid_mfma(
@@ -346,7 +339,6 @@ __device__ __forceinline__ void degrid_mfma(
   };
   int e = 0;
   static_assert(KP / 2 <= kThreads, "one K-block per thread in a single chunk");
-  constexpr bool kChunkScale = IDG_DEGRID_CHUNK_SCALE != 0;
   if (single) {
     // one chunk: every thread computes its K-block's entries once (NW = 8:
     // the upper half repeats the last K-block, for the max only), the
@@ -361,49 +353,26 @@ __device__ __forceinline__ void degrid_mfma(
     e = scale_exp(2.0f * block_max(v));
     if (has_block) store_block(tid, k, ldexpf(1.0f, IDG_DEGRID_BSCALE - e));
     __syncthreads();
-  } else if constexpr (!kChunkScale) {
-    float v = 0.0f;
-    for (int p = tid; p < npix; p += kThreads) {
-      float4 pa, pb, geo;
-      pixel_entry(p, S, npix, image_size, g, nr_stations, spheroidal, aterms,
-                  sg, pa, pb, geo);
-      v = fmaxf(v, absmax(pa, pb));
-    }
-    e = scale_exp(2.0f * block_max(v));
   }
   float scale = ldexpf(1.0f, IDG_DEGRID_BSCALE - e),
         unscale = ldexpf(1.0f, e - IDG_DEGRID_BSCALE);
-  // B fragments and geometry of pairs [pc0, pc0 + KP): one thread per
-  // K-block (2 pairs), writing all 16 column lanes of it.
+  // B fragments and geometry of pairs [pc0, pc0 + KP) of a subgrid of
+  // several chunks, with the chunk's own scale: every thread's K-block
+  // entries (2 pairs; the last K-block again past KP/2, for the maximum
+  // only), the workgroup maximum, then the split, writing all 16 column
+  // lanes of the K-block -- the single chunk's steps, per chunk
   auto build = [&](int pc0) {
-    if constexpr (kChunkScale) {
-      // the chunk's own scale: every thread's K-block entries (the last
-      // K-block again past KP/2, for the maximum only), the workgroup
-      // maximum, then the split -- the single chunk's steps, per chunk
-      Block k;
-      const bool has_block = tid < KP / 2;
-      entries(pc0, has_block ? tid : KP / 2 - 1, k);
-      float v = 0.0f;
+    Block k;
+    const bool has_block = tid < KP / 2;
+    entries(pc0, has_block ? tid : KP / 2 - 1, k);
+    float v = 0.0f;
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
-        v = fmaxf(v, fmaxf(absmax(k.pa[h], k.pb[h]), absmax(k.ma[h], k.mb[h])));
-      const int ec = scale_exp(2.0f * block_max(v));
-      scale = ldexpf(1.0f, IDG_DEGRID_BSCALE - ec);
-      unscale = ldexpf(1.0f, ec - IDG_DEGRID_BSCALE);
-      if (has_block) store_block(tid, k, scale);
-      return;
-    }
-    // an opaque copy of tid per call: the addresses derived from it are
-    // formed here, not hoisted out of the chunk loop and kept live across
-    // the MFMA loops (they were spilled: scratch 92 -> 36 B/lane at S = 32,
-    // degridder counter traffic 2.95 -> 2.70 GB per launch)
-    int q0 = tid;
-    asm volatile("" : "+v"(q0));
-    for (int q = q0; q < KP / 2; q += kThreads) {
-      Block k;
-      entries(pc0, q, k);
-      store_block(q, k, scale);
-    }
+    for (int h = 0; h < 2; ++h)
+      v = fmaxf(v, fmaxf(absmax(k.pa[h], k.pb[h]), absmax(k.ma[h], k.mb[h])));
+    const int ec = scale_exp(2.0f * block_max(v));
+    scale = ldexpf(1.0f, IDG_DEGRID_BSCALE - ec);
+    unscale = ldexpf(1.0f, ec - IDG_DEGRID_BSCALE);
+    if (has_block) store_block(tid, k, scale);
   };
 
   // Chunks of KP pairs are the outermost loop so that building the next
@@ -740,22 +709,9 @@ __global__ void __launch_bounds__(MODE == 1 ? 64 * NW : kBlock,
 // KP = 1,024 single pixels (one thread per
 // K-block of the 512), so an S = 32 subgrid is one chunk and its
 // visibilities are written once (the combined kernel's 512-pixel chunks
-// read them back and wrote them again).
-// IDG_DEGRID_KP64=512: the S = 64 8-wave mirror kernel keeps 512-pair
-// chunks (A/B); the two-kernel form takes the 8-wave one at S = 64
-#ifndef IDG_DEGRID_KP64
-#define IDG_DEGRID_KP64 1024
-#endif
-constexpr int mirror_kp64() { return IDG_DEGRID_KP64; }
-
-// KPX > 0: pairs per chunk (else as below); KS: K split (degrid_mfma).
-// The S = 64 single-chunk form (round 6): KPX = 2,048 -- the whole
-// subgrid's pairs, 160 KB of LDS, one 16-wave workgroup per CU in two K
-// groups of 8 waves -- so the visibilities are written once
-// instead of written, read back and written again (the two-chunk form's
-// 2.08x the algorithmic bytes, profiles/r05/kernels_s64).
-template <int S_CT, int CT, int NW, bool TAIL = true, int KPX = 0,
-          int KS = 1>
+// read them back and wrote them again).  At S = 64 the two-kernel form
+// takes the 8-wave mirror kernel.
+template <int S_CT, int CT, int NW, bool TAIL = true>
 __global__ void __launch_bounds__(64 * NW, IDG_DEGRID_WAVES)
     kernel_degridder_mirror_mi355x(
         const int grid_size, int subgrid_size, float image_size,
@@ -772,8 +728,7 @@ __global__ void __launch_bounds__(64 * NW, IDG_DEGRID_WAVES)
   // four, and its visibilities are written, read back and written again
   // once instead of three times (profiles/r04/kernels_s64: 18.7 GB per
   // launch against 4.85 GB algorithmic)
-  constexpr int KP =
-      KPX > 0 ? KPX : (S_CT == 64 && NW == 8) ? mirror_kp64() : 512;
+  constexpr int KP = (S_CT == 64 && NW == 8) ? 1024 : 512;
   __shared__ unsigned lds[DegridMfmaLds<KP>::kWords];
   const int S = S_CT > 0 ? S_CT : subgrid_size;
   const int npix = S * S;
@@ -795,26 +750,10 @@ __global__ void __launch_bounds__(64 * NW, IDG_DEGRID_WAVES)
     if (tid == 0) queue_push(queue, gridDim.x, s);
     return;
   }
-  degrid_mfma<S_CT, CT, IDG_DEGRID_CB, KP, true, NW, TAIL, KS>(
+  degrid_mfma<S_CT, CT, IDG_DEGRID_CB, KP, true, NW, TAIL>(
       g, S, npix, image_size, nr_channels, nr_stations, uvw, wavenumbers,
       visibilities, spheroidal, aterms,
       subgrids + static_cast<size_t>(s) * 4 * npix, lds);
-}
-
-// IDG_DEGRID_S64=1: the S = 64 mirror kernel of the two-kernel form in the
-// single-chunk form above; 2 (default): the two-chunk form (8 waves,
-// 1,024-pair chunks).  Measured on one box (profiles/r06/s64_single/): the
-// single chunk moves 7.01 GB per launch against 10.09 (5.23 GB with the
-// channel groups split instead of K, at 33.7 ms) but runs 32.5 ms against
-// 29.3: with one workgroup per CU nothing overlaps its chunk build and the
-// partial-sum hand-over, which the two-chunk form's second workgroup hides.
-#ifndef IDG_DEGRID_S64
-#define IDG_DEGRID_S64 2
-#endif
-template <bool TAIL>
-const void *degridder_mirror_s64_single() {
-  return reinterpret_cast<const void *>(
-      &kernel_degridder_mirror_mi355x<64, IDG_DEGRID_CT, 16, TAIL, 2048, 2>);
 }
 
 template <int S_CT, int CT, bool TAIL = true>
@@ -929,12 +868,6 @@ DegridderSet degridder_set_for(bool nw8, bool tail) {
   return tail ? degridder_set<S_, 4, true>() : degridder_set<S_, 4, false>();
 }
 
-// IDG_DEGRID_SPLIT=0: the device entries launch the one combined MFMA
-// kernel (A/B of the two-launch form).
-#ifndef IDG_DEGRID_SPLIT
-#define IDG_DEGRID_SPLIT 1
-#endif
-
 // IDG_DEGRIDDER_IMPL=valu selects the VALU mirror path (A/B comparisons).
 static int degridder_impl() {
   const char *v = std::getenv("IDG_DEGRIDDER_IMPL");
@@ -976,14 +909,10 @@ KernelChoice select_degridder(const Problem &p) {
     // the MFMA kernel has no CG
     k.func = set.combined;
     k.block = nw8 ? 512 : 256;
-    if (IDG_DEGRID_SPLIT && two_kernel_form(p.nr_subgrids)) {
+    if (two_kernel_form(p.nr_subgrids)) {
       // mirror-eligible subgrids (even S only), then the others on 8-wave
       // workgroups with 1,024-pixel chunks
-      if (s64 && IDG_DEGRID_S64 == 1)  // 16 waves, one 2,048-pair chunk
-        k.parts[0] = {tail ? degridder_mirror_s64_single<true>()
-                           : degridder_mirror_s64_single<false>(),
-                      1024, KernelChoice::kMirror};
-      else if (s64 && mirror_kp64() > 512)  // 8 waves, 1,024-pair chunks
+      if (s64)  // 8 waves, 1,024-pair chunks
         k.parts[0] = {degridder_set_for<64>(true, tail).mirror, 512,
                       KernelChoice::kMirror};
       else if (p.subgrid_size % 2 == 0)

@@ -57,11 +57,8 @@ constexpr float kPhaseTail = 0x1.5a892p-25f;  // 4.034206e-8
 // c = k_b * (-phase_index) * (1/2pi - kInv2PiHi) in revolutions for a
 // packed pair of -phase_index (the gridder's sign; the degridder passes
 // +phase_index for its phase = k * phase_index - phase_offset).
-#ifndef IDG_TAIL_K
-#define IDG_TAIL_K 1
-#endif
 __device__ __forceinline__ floatx2 tail_k_rev(floatx2 neg_pidx, float kb) {
-  const float f = IDG_TAIL_K ? kb * kInv2PiLo : 0.0f;
+  const float f = kb * kInv2PiLo;
   return neg_pidx * floatx2{f, f};
 }
 
@@ -122,27 +119,8 @@ __device__ __forceinline__ void rotate4(float (&v)[8], float c, float s) {
 // never by the hardware's own [-256, 256] fold of a large, already-rounded
 // argument (the trap of __sinf/__cosf).
 __device__ __forceinline__ void sincos_rev(float r, float *s, float *c) {
-#if IDG_SINCOS_POLY
-  // Minimax-free fallback: quadrant split + Cody-Waite style polynomials.
-  const float q = __builtin_rintf(4.0f * r);
-  const float g = fma_(q, -0.25f, r);  // |g| <= 1/8 revolution, exact
-  const float x = g * 6.28318530717958647692f;
-  const float z = x * x;
-  float sp = fma_(fma_(-1.9515295891e-4f, z, 8.3321608736e-3f), z,
-                  -1.6666654611e-1f);
-  const float sn = fma_(sp * z, x, x);
-  float cp = fma_(fma_(2.443315711809948e-5f, z, -1.388731625493765e-3f), z,
-                  4.166664568298827e-2f);
-  const float cs = fma_(cp * z, z, fma_(-0.5f, z, 1.0f));
-  const int qi = static_cast<int>(q) & 3;
-  const float s0 = (qi & 1) ? cs : sn;
-  const float c0 = (qi & 1) ? sn : cs;
-  *s = (qi & 2) ? -s0 : s0;
-  *c = ((qi + 1) & 2) ? -c0 : c0;
-#else
   *s = __builtin_amdgcn_sinf(r);
   *c = __builtin_amdgcn_cosf(r);
-#endif
 }
 
 // Subgrid of workgroup `orig` among nwg: blocks are dealt round-robin over
@@ -152,12 +130,8 @@ __device__ __forceinline__ void sincos_rev(float r, float *s, float *c) {
 // stations, so their A-term reads hit the same L2.  A speed choice only:
 // any placement computes the same outputs.
 __device__ __forceinline__ int xcd_subgrid(int orig, int nwg) {
-#ifdef IDG_NO_XCD_REMAP
-  return orig;
-#else
   const int q = nwg / 8, r = nwg % 8, x = orig % 8;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + orig / 8;
-#endif
 }
 
 // The general-subgrid queue of the two-kernel launch (util.hpp
@@ -172,10 +146,9 @@ __device__ __forceinline__ int xcd_subgrid(int orig, int nwg) {
 // are zero before a launch pair: zeroed when the workspace is allocated, and
 // zeroed again by the general kernel's last workgroup to finish
 // (queue_retire), so a workspace cached per stream needs no clear per launch.
-// (A persistent mirror kernel's take counter and exit count sit at
-// kQueueMirror / kQueueMirrorExit, zeroed by its own last workgroup.)
+// (Ints (kQueueExit, kQueueHead) are unused.)
 constexpr int kQueueShards = 8, kQueueNext = 256, kQueueExit = 257,
-              kQueueMirror = 264, kQueueMirrorExit = 272, kQueueHead = 288;
+              kQueueHead = 288;
 
 __host__ __device__ inline int queue_cap(int ns) {
   return (ns + kQueueShards - 1) / kQueueShards;

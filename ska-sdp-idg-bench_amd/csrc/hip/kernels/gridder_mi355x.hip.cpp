@@ -54,18 +54,10 @@
 #ifndef IDG_GRID_WAVES_GENERAL
 #define IDG_GRID_WAVES_GENERAL 4
 #endif
-// general path (w != 0): X + Y in one accumulator tile, 2 PT tiles per wave
-#ifndef IDG_GRID_FUSED_GENERAL
-#define IDG_GRID_FUSED_GENERAL 1
-#endif
 // the B operand's (visibilities') power-of-two scale targets a first-fill
 // maximum in [2^(kBS-1), 2^kBS)
 #ifndef IDG_GRID_BSCALE
 #define IDG_GRID_BSCALE 12
-#endif
-// non-temporal B-fill loads (A/B; see the fill loop)
-#ifndef IDG_GRID_NT_FILL
-#define IDG_GRID_NT_FILL 0
 #endif
 // waves per workgroup of the MFMA kernel (the VALU kernel uses kBlock)
 #ifndef IDG_GRID_NW
@@ -345,7 +337,7 @@ __device__ __forceinline__ void l2_prefetch_dma(const void *src,
 // the subgrid's own output slot (32 KB at S = 32, one pass), which only the
 // epilogue writes, after the master is read back.
 template <int S_CT, int PT, int CB, int NW, bool MIRROR, bool FFT = false,
-          int PREC = kPrecTail, bool PRESCAN = false, bool OPAQUE_TID = !MIRROR,
+          int PREC = kPrecTail, bool PRESCAN = false,
           int FILL_D = IDG_GRID_FILL_DEPTH>
 __device__ __forceinline__ void grid_mfma(
     const SubgridSetup &g, int S, int npix, float image_size, int C,
@@ -356,13 +348,13 @@ __device__ __forceinline__ void grid_mfma(
     float2 *__restrict__ out, unsigned *lds, float vmax_pre = 0.0f,
     int pass_lo = 0, int pass_hi = 1 << 30) {
   static_assert(CB % 4 == 0, "anchor blocks hold whole channel quads");
-  // General path (and the persistent mirror kernel): an opaque copy of the
-  // thread index, so values derived from it are formed per call, not hoisted
-  // out of the kernel's loop over subgrids and kept live (spilled) across it
-  // (scratch 408 -> 160 B/lane gridder, 168 -> 68 degridder at S = 32; the
-  // mirror path, one subgrid per workgroup, is better without it).
+  // General path: an opaque copy of the thread index, so values derived from
+  // it are formed per call, not hoisted out of the kernel's loop over
+  // subgrids and kept live (spilled) across it (scratch 408 -> 160 B/lane
+  // gridder, 168 -> 68 degridder at S = 32; the mirror path, one subgrid per
+  // workgroup, is better without it).
   int tid = threadIdx.x;
-  if constexpr (OPAQUE_TID) asm volatile("" : "+v"(tid));
+  if constexpr (!MIRROR) asm volatile("" : "+v"(tid));
   const int lane = tid & 63, wave = tid >> 6;
   const int grp = lane >> 4, col = lane & 15;
   // MIRROR: base pixels b < npix/2 (mirror npix-1-b shares the phasor);
@@ -371,11 +363,10 @@ __device__ __forceinline__ void grid_mfma(
   // General path: X + Y accumulate into one tile (nothing to mirror), so a
   // wave holds twice the pixel tiles in the same accumulator registers and
   // the S = 32 subgrid is one pass (B built once per subgrid, not twice).
-  constexpr bool kFused = !MIRROR && IDG_GRID_FUSED_GENERAL;
   // the reduction tail on every phasor, or 4x on one channel per quad
   constexpr bool kTailAlt = (PREC & kPrecTailAlt) != 0;
   constexpr bool kTailAll = (PREC & kPrecTail) != 0 && !kTailAlt;
-  constexpr int AT = kFused ? PT : 2 * PT;  // accumulator tiles per wave
+  constexpr int AT = MIRROR ? 2 * PT : PT;  // accumulator tiles per wave
   using Lds = MfmaLds<AT, NW>;
   // General path at S = 32: the pixel geometry lives in LDS, not in 32
   // VGPRs across the whole subgrid (the general path's spills).  A lane's
@@ -383,7 +374,7 @@ __device__ __forceinline__ void grid_mfma(
   // by column col and col + 16 for every pair, m wave-uniform per pair
   // (row wave PT / 2 + h), n and phase_offset read per pair and timestep
   // quad.
-  constexpr bool kGeoLds = kFused && S_CT == 32;
+  constexpr bool kGeoLds = !MIRROR && S_CT == 32;
   float *geo = reinterpret_cast<float *>(lds + Lds::kGeoOff);
   const int nt = g.nr_timesteps;
   const int nchq = (C + 3) / 4;  // channel quads
@@ -485,7 +476,7 @@ __device__ __forceinline__ void grid_mfma(
         PG2[i / 2][i % 2] = pg;
       }
     }
-    constexpr int PY = kFused ? 1 : PT;  // separate Y tiles (mirror path)
+    constexpr int PY = MIRROR ? PT : 1;  // separate Y tiles (mirror path)
     floatx4 accx[PT], accy[PY];
 #pragma unroll
     for (int i = 0; i < PT; ++i) accx[i] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -560,13 +551,6 @@ __device__ __forceinline__ void grid_mfma(
           const unsigned off_s = (grp * C * 8 + w_s) * 4u;
           int qq = wv / nj, jj = wv - (wv / nj) * nj;
           float lmax = 0.0f;  // max |raw value| this lane loads
-#ifdef IDG_DEBUG_SKIPFILL
-          // timing experiment only (wrong output): every fill after the
-          // first reuses its B fragments
-          const int ks_first = fidx > 0 ? nks : wv;
-#else
-          const int ks_first = wv;
-#endif
           if constexpr (kOneFrag) {
             // One fragment per (K-step, lane), Bc: the sin GEMM multiplies
             // it too and the epilogue maps Y' = s * Bc to Y = s * Bs.  Four
@@ -578,19 +562,8 @@ __device__ __forceinline__ void grid_mfma(
                 const char *blk = reinterpret_cast<const char *>(
                     vsubf + ((q0 + q_) * 4 * C + c0) * 8);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-#if IDG_GRID_NT_FILL
-                  const __amdgpu_buffer_rsrc_t rsrc =
-                      __builtin_amdgcn_make_buffer_rsrc(
-                          const_cast<char *>(blk), static_cast<short>(0),
-                          0x7ffffff0, 0x00020000);
-                  b[u] = __builtin_bit_cast(
-                      float, __builtin_amdgcn_raw_buffer_load_b32(
-                                 rsrc, static_cast<int>(off_c), 32 * u, 2));
-#else
+                for (int u = 0; u < 4; ++u)
                   b[u] = *reinterpret_cast<const float *>(blk + off_c + 32 * u);
-#endif
-                }
               } else {
                 const int t = (q0 + q_) * 4 + grp;
 #pragma unroll
@@ -617,7 +590,7 @@ __device__ __forceinline__ void grid_mfma(
               }
             };
             constexpr int D = FILL_D;
-            for (int ks = ks_first; ks < nks; ks += D * NW) {
+            for (int ks = wv; ks < nks; ks += D * NW) {
               float b[D][4];
 #pragma unroll
               for (int d = 0; d < D; ++d)
@@ -631,7 +604,7 @@ __device__ __forceinline__ void grid_mfma(
             }
           } else {
           // general path: [X, Y] fragments, Bc and Bs
-          for (int ks = ks_first; ks < nks; ks += NW) {
+          for (int ks = wv; ks < nks; ks += NW) {
             const int t = (q0 + qq) * 4 + grp;
             const int c0 = 4 * (j0 + jj);
             float bc[4], bs[4];
@@ -640,26 +613,10 @@ __device__ __forceinline__ void grid_mfma(
                   vsubf + ((q0 + qq) * 4 * C + c0) * 8);
 #pragma unroll
               for (int u = 0; u < 4; ++u) {
-#if IDG_GRID_NT_FILL
-                // the fill is the rows' last use: non-temporal (a raw buffer
-                // load keeps the SGPR-base + VGPR-offset form), so L2 keeps
-                // the blocked-summation masters rather than spent rows
-                const __amdgpu_buffer_rsrc_t rsrc =
-                    __builtin_amdgcn_make_buffer_rsrc(
-                        const_cast<char *>(blk), static_cast<short>(0),
-                        0x7ffffff0, 0x00020000);
-                const float rc = __builtin_bit_cast(
-                    float, __builtin_amdgcn_raw_buffer_load_b32(
-                               rsrc, static_cast<int>(off_c), 32 * u, 2));
-                const float rs = __builtin_bit_cast(
-                    float, __builtin_amdgcn_raw_buffer_load_b32(
-                               rsrc, static_cast<int>(off_s), 32 * u, 2));
-#else
                 const float rc =
                     *reinterpret_cast<const float *>(blk + off_c + 32 * u);
                 const float rs =
                     *reinterpret_cast<const float *>(blk + off_s + 32 * u);
-#endif
                 lmax = fmaxf(lmax, fmaxf(fabsf(rc), fabsf(rs)));
                 bc[u] = rc * scale;
                 bs[u] = rs * sc_s;
@@ -770,7 +727,7 @@ __device__ __forceinline__ void grid_mfma(
             const idg::UVWCoordinate<float> c = {c4.x, c4.y, c4.z};
             const floatx2 cu = {c.u, c.u}, cv = {c.v, c.v};
             const floatx2 ih = {kInv2PiHi, kInv2PiHi};
-            if constexpr (kFused) {
+            if constexpr (!MIRROR) {
               // Tile pairs outermost: only one pair's phase terms are live,
               // and each K-step's B fragments are re-read from LDS per pair.
 #pragma unroll
@@ -837,10 +794,8 @@ __device__ __forceinline__ void grid_mfma(
             for (int h = 0; h < PH; ++h) {
               // phase_index = fma(w, n, fma(u, l, v*m)); w = 0 on mirror
               // subgrids, where fma(0, n, x) == x
-              floatx2 pidx = __builtin_elementwise_fma(cu, L2[h], cv * M2[h]);
-              if constexpr (!MIRROR)
-                pidx = __builtin_elementwise_fma(floatx2{c.w, c.w}, N2[h],
-                                                 pidx);
+              const floatx2 pidx =
+                  __builtin_elementwise_fma(cu, L2[h], cv * M2[h]);
               NP[h] = -pidx;
               // -m: the whole revolutions of the block's first-channel
               // phase, so every r below stays within ~0.7 revolutions
@@ -918,7 +873,7 @@ __device__ __forceinline__ void grid_mfma(
             const float unsc = ldexpf(1.0f, e - kBS);
 #pragma unroll
             for (int i = 0; i < PT; ++i) flush_tile(accx[i], i, unsc);
-            if constexpr (!kFused) {
+            if constexpr (MIRROR) {
 #pragma unroll
               for (int i = 0; i < PY; ++i) flush_tile(accy[i], PT + i, unsc);
             }
@@ -937,7 +892,7 @@ __device__ __forceinline__ void grid_mfma(
           const float4 m = *master(i);
           accx[i] += floatx4{m.x, m.y, m.z, m.w} * sc;
         }
-        if constexpr (!kFused) {
+        if constexpr (MIRROR) {
 #pragma unroll
           for (int i = 0; i < PY; ++i) {
             const float4 m = *master(PT + i);
@@ -957,7 +912,7 @@ __device__ __forceinline__ void grid_mfma(
       for (int r = 0; r < 4; ++r) {
         const int lp = (wave * PT + i) * 16 + grp * 4 + r;
         obuf[lp * 16 + col] = accx[i][r];
-        if constexpr (!kFused) obuf[(kPass + lp) * 16 + col] = accy[i][r];
+        if constexpr (MIRROR) obuf[(kPass + lp) * 16 + col] = accy[i][r];
       }
     __syncthreads();
     // FFT: each thread's pixels stay in registers until every obuf row is
@@ -981,7 +936,7 @@ __device__ __forceinline__ void grid_mfma(
                           xh0.w + xl0.w, xh1.x + xl1.x, xh1.y + xl1.y,
                           xh1.z + xl1.z, xh1.w + xl1.w};
       float y[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      if constexpr (!kFused) {  // the Y tiles (fused: already in x)
+      if constexpr (MIRROR) {  // the Y tiles (general: already in x)
         const float4 *yr =
             reinterpret_cast<const float4 *>(obuf + (kPass + q) * 16);
         const float4 yh0 = yr[0], yh1 = yr[1], yl0 = yr[2], yl1 = yr[3];
@@ -1011,7 +966,7 @@ __device__ __forceinline__ void grid_mfma(
       float ab[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        ab[j] = (kFused ? x[j] : x[j] + y[j]) * unscale;
+        ab[j] = (MIRROR ? x[j] + y[j] : x[j]) * unscale;
       rotate4(ab, tc, ts);
       emit(ab, b, it, 0);
       if constexpr (MIRROR) {
@@ -1161,15 +1116,14 @@ __global__ void __launch_bounds__(MODE == 1 ? 64 * IDG_GRID_NW : kBlock,
         S % 2 == 0 && g.w_offset == 0.0f;
     const float vmax = prologue_max<NW>(red);
     if (mirror)
-      grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true, false,
+      grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true,
                 mirror_fill_depth(S_CT, true)>(
           g, S, npix, image_size, C, nr_stations, uvw, wavenumbers,
           visibilities, spheroidal, aterms, out, lds, vmax);
     else
-      grid_mfma<S_CT, IDG_GRID_FUSED_GENERAL ? 2 * PT : PT, CB, NW, false,
-                FFT, PREC, true>(g, S, npix, image_size, C, nr_stations, uvw,
-                                 wavenumbers, visibilities, spheroidal, aterms,
-                                 out, lds, vmax);
+      grid_mfma<S_CT, 2 * PT, CB, NW, false, FFT, PREC, true>(
+          g, S, npix, image_size, C, nr_stations, uvw, wavenumbers,
+          visibilities, spheroidal, aterms, out, lds, vmax);
 #if defined(IDG_WG_TIMELINE) && IDG_WG_TIMELINE
     timeline_end(idg_debug_timeline_gridder);
 #endif
@@ -1324,73 +1278,13 @@ __global__ void __launch_bounds__(64 * IDG_GRID_NW, IDG_GRID_WAVES)
   static_assert(SPLIT == 1 || (S_CT > 0 && SPLIT * kPass >= S_CT * S_CT / 2 &&
                                (SPLIT - 1) * kPass < S_CT * S_CT / 2),
                 "mirror_split(S) does not match the pass size");
-  grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true, false,
+  grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true,
             mirror_fill_depth(S_CT, false)>(
       g, S, npix, image_size, nr_channels, nr_stations, uvw, wavenumbers,
       visibilities, spheroidal, aterms,
       subgrids + static_cast<size_t>(s) * 4 * npix, lds,
       prologue_max<NW>(red), SPLIT > 1 ? q * kPass : 0,
       SPLIT > 1 ? (q + 1) * kPass : 1 << 30);
-}
-
-// The persistent form of the mirror kernel (A/B builds, -DIDG_GRID_PERSIST=1;
-// round 6, the review's N = 8 item): a resident grid (occupancy x CUs, at
-// most nr_subgrids) whose workgroups take subgrids 0 .. nr_subgrids-1 from a
-// take counter in the queue workspace (kQueueMirror), the next index
-// requested while the current subgrid runs, and grid each exactly as
-// kernel_gridder_mirror_mi355x does (bit for bit: the same grid_mfma on the
-// same subgrid).  The last workgroup to leave zeroes the counter and its
-// exit count (kQueueMirrorExit) for the next launch.
-template <int S_CT, int CB, int PT, bool FFT = false, int PREC = kPrecTail>
-__global__ void __launch_bounds__(64 * IDG_GRID_NW, IDG_GRID_WAVES)
-    kernel_gridder_mirror_persist_mi355x(
-        const int grid_size, int subgrid_size, float image_size,
-        float w_step_in_lambda, int nr_channels, int nr_stations,
-        const idg::UVWCoordinate<float> *__restrict__ uvw,
-        const float *__restrict__ wavenumbers,
-        const float2 *__restrict__ visibilities,
-        const float *__restrict__ spheroidal,
-        const float2 *__restrict__ aterms,
-        const idg::Metadata *__restrict__ metadata,
-        float2 *__restrict__ subgrids, int *__restrict__ queue,
-        int nr_subgrids) {
-  constexpr int NW = IDG_GRID_NW;
-  __shared__ unsigned lds[MfmaLds<2 * PT, NW>::kWords];
-  __shared__ int take;
-  const int S = S_CT > 0 ? S_CT : subgrid_size;
-  const int npix = S * S;
-  const int tid = threadIdx.x;
-  if (tid == 0) take = atomicAdd(queue + kQueueMirror, 1);
-  __syncthreads();
-  int i = __builtin_amdgcn_readfirstlane(take);
-  while (i < nr_subgrids) {
-    __syncthreads();  // every thread has read `take`
-    if (tid == 0) take = atomicAdd(queue + kQueueMirror, 1);  // lands later
-    const int s = i;
-    const SubgridSetup g = setup_subgrid(metadata, s, grid_size, S,
-                                         image_size, w_step_in_lambda);
-    float *red = reinterpret_cast<float *>(lds + MfmaLds<2 * PT, NW>::kRedOff);
-    const bool mirror =
-        __syncthreads_or(prologue_scan<NW>(g, nr_channels, uvw, visibilities,
-                                           red)) == 0 &&
-        S % 2 == 0 && g.w_offset == 0.0f;
-    if (!mirror) {
-      if (tid == 0) queue_push(queue, nr_subgrids, s, s % kQueueShards);
-    } else {
-      grid_mfma<S_CT, PT, CB, NW, true, FFT, PREC, true, true>(
-          g, S, npix, image_size, nr_channels, nr_stations, uvw, wavenumbers,
-          visibilities, spheroidal, aterms,
-          subgrids + static_cast<size_t>(s) * 4 * npix, lds,
-          prologue_max<NW>(red), 0, 1 << 30);
-    }
-    __syncthreads();  // `take` has landed; the subgrid's LDS is consumed
-    i = __builtin_amdgcn_readfirstlane(take);
-  }
-  if (tid == 0 && atomicAdd(queue + kQueueMirrorExit, 1) ==
-                      static_cast<int>(gridDim.x) - 1) {
-    queue[kQueueMirror] = 0;
-    queue[kQueueMirrorExit] = 0;
-  }
 }
 
 template <int S_CT, int CB, int PT, bool FFT = false, int PREC = kPrecTail>
@@ -1431,8 +1325,7 @@ __global__ void __launch_bounds__(64 * IDG_GRID_NW, IDG_GRID_WAVES_GENERAL)
     const int s = all ? i : qv.at(i);
     const SubgridSetup g = setup_subgrid(metadata, s, grid_size, S,
                                          image_size, w_step_in_lambda);
-    grid_mfma<S_CT, IDG_GRID_FUSED_GENERAL ? 2 * PT : PT, CB, NW, false, FFT,
-              PREC>(
+    grid_mfma<S_CT, 2 * PT, CB, NW, false, FFT, PREC>(
         g, S, npix, image_size, nr_channels, nr_stations, uvw, wavenumbers,
         visibilities, spheroidal, aterms,
         subgrids + static_cast<size_t>(s) * 4 * npix, lds);
@@ -1451,34 +1344,15 @@ struct GridderSet {
   const void *combined, *mirror, *general;
 };
 // The mirror kernel's workgroups per subgrid: the four S = 64 passes on
-// four workgroups (IDG_GRID_SPLIT64=0: one, the A/B).
-#ifndef IDG_GRID_SPLIT64
-#define IDG_GRID_SPLIT64 1
-#endif
-// IDG_GRID_PERSIST=1 (A/B builds): the S = 32 mirror kernel in its
-// persistent form (kernel_gridder_mirror_persist_mi355x).
-#ifndef IDG_GRID_PERSIST
-#define IDG_GRID_PERSIST 0
-#endif
-constexpr int mirror_split(int S) {
-  return S == 64 && IDG_GRID_SPLIT64 ? 4 : 1;
-}
-template <int S_, bool FFT_, int PREC_>
-const void *mirror_kernel() {
-  if constexpr (IDG_GRID_PERSIST && S_ == 32)
-    return reinterpret_cast<const void *>(
-        &kernel_gridder_mirror_persist_mi355x<S_, 16, IDG_GRID_PT, FFT_,
-                                              PREC_>);
-  else
-    return reinterpret_cast<const void *>(
-        &kernel_gridder_mirror_mi355x<S_, 16, IDG_GRID_PT, FFT_, PREC_,
-                                      mirror_split(S_)>);
-}
+// four workgroups.
+constexpr int mirror_split(int S) { return S == 64 ? 4 : 1; }
 template <int S_, int PPT_, bool FFT_, int PREC_>
 GridderSet gridder_set() {
   return {reinterpret_cast<const void *>(
               &kernel_gridder_mi355x<S_, PPT_, 16, 1, IDG_GRID_PT, FFT_, PREC_>),
-          mirror_kernel<S_, FFT_, PREC_>(),
+          reinterpret_cast<const void *>(
+              &kernel_gridder_mirror_mi355x<S_, 16, IDG_GRID_PT, FFT_, PREC_,
+                                            mirror_split(S_)>),
           reinterpret_cast<const void *>(
               &kernel_gridder_general_mi355x<S_, 16, IDG_GRID_PT, FFT_, PREC_>)};
 }
@@ -1508,12 +1382,6 @@ GridderSet gridder_set_for(int prec) {
 #define IDG_GRIDDER_VALU(S_, PPT_)                                        \
   reinterpret_cast<const void *>(                                         \
       &kernel_gridder_mi355x<S_, PPT_, 16, 0, IDG_GRID_PT>)
-
-// IDG_GRID_SPLIT=0: the device entries launch the one combined MFMA kernel
-// (A/B of the two-launch form).
-#ifndef IDG_GRID_SPLIT
-#define IDG_GRID_SPLIT 1
-#endif
 
 // IDG_GRIDDER_IMPL=valu selects the VALU mirror path (A/B comparisons);
 // IDG_GRIDDER_IMPL=sequential the order-preserving kernel, bit-exact to the
@@ -1586,12 +1454,10 @@ KernelChoice select_gridder(const Problem &p) {
       break;
   }
   k.func = set.combined;
-  if (mfma && IDG_GRID_SPLIT && two_kernel_form(p.nr_subgrids)) {
+  if (mfma && two_kernel_form(p.nr_subgrids)) {
     if (set.mirror)
       k.parts[0] = {set.mirror, k.block, KernelChoice::kMirror,
-                    p.subgrid_size == 64 ? mirror_split(64)
-                    : IDG_GRID_PERSIST && p.subgrid_size == 32 ? 0
-                                                               : 1};
+                    mirror_split(p.subgrid_size)};
     k.parts[1] = {set.general, k.block, KernelChoice::kGeneral};
     // no subgrid mirror-eligible: the combined kernel, one workgroup per
     // subgrid (2.7 % faster on a w-term batch than the queue-fed kernel)

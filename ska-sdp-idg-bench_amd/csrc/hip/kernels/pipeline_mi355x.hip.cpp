@@ -54,25 +54,14 @@ __device__ __forceinline__ int half_shift(int v, int S) {
 // a later kernel): non-temporal, so they do not sit dirty in L2 / MALL and
 // the next kernel does not pay for their write-back (measured: splitter
 // 0.266 -> 0.256 ms and the inverse FFT after it 0.306 -> 0.270 ms).
-#ifndef IDG_PIPE_NT
-#define IDG_PIPE_NT 1
-#endif
 __device__ __forceinline__ void store_stream(float2 *p, float2 v) {
-#if IDG_PIPE_NT
   typedef float f2 __attribute__((ext_vector_type(2)));
   __builtin_nontemporal_store(f2{v.x, v.y}, reinterpret_cast<f2 *>(p));
-#else
-  *p = v;
-#endif
 }
 __device__ __forceinline__ void store_stream(float4 *p, float4 v) {
-#if IDG_PIPE_NT
   typedef float f4 __attribute__((ext_vector_type(4)));
   __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w},
                               reinterpret_cast<f4 *>(p));
-#else
-  *p = v;
-#endif
 }
 
 __device__ __forceinline__ bool fits(const idg::Metadata &m, int G, int S,
@@ -158,9 +147,6 @@ __global__ void __launch_bounds__(256)
 #endif
 #ifndef IDG_ADD_U
 #define IDG_ADD_U 4
-#endif
-#ifndef IDG_ADD_MASKED
-#define IDG_ADD_MASKED 1
 #endif
 constexpr int kTW = IDG_ADD_TW;  // grid tile width (pixels)
 constexpr int kTH = IDG_ADD_TH;  // grid tile height
@@ -627,7 +613,6 @@ __global__ void __launch_bounds__(256)
             ph[hh][j] = !ok[hh][j] ? make_float2(0.0f, 0.0f)
                         : tabled   ? table[x + y]
                                    : shift_phasor(x, y, S, 1.0f);
-#if IDG_ADD_MASKED
             // lanes outside the entry's subgrid issue no load (a wave with
             // none inside skips the entry's loads)
             if (ok[hh][j]) {
@@ -639,11 +624,6 @@ __global__ void __launch_bounds__(256)
               for (int pol = 0; pol < 4; ++pol)
                 v[hh][j][pol] = make_float2(0.f, 0.f);
             }
-#else
-#pragma unroll
-            for (int pol = 0; pol < 4; ++pol)
-              v[hh][j][pol] = sg[pol * npix + src];
-#endif
           }
         }
 #pragma unroll

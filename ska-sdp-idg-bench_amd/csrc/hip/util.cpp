@@ -464,13 +464,8 @@ hipError_t launch_parts(const KernelChoice &k, int nr_subgrids, void **args13,
   void *args[16];
   for (int i = 0; i < 13; ++i) args[i] = args13[i];
   args[13] = &queue;
-  args[14] = &ns;  // (read by a persistent mirror kernel only)
-  // per_subgrid 0: a persistent mirror kernel, a resident grid
-  const int mirror_grid =
-      mirror.per_subgrid > 0
-          ? nr_subgrids * mirror.per_subgrid
-          : std::min(nr_subgrids,
-                     std::max(1, resident_workgroups(mirror.func, mirror.block)));
+  args[14] = &ns;  // (the general kernel's; the mirror kernel takes 14)
+  const int mirror_grid = nr_subgrids * mirror.per_subgrid;
   if (err == hipSuccess && run_mirror)
     err = hipLaunchKernel(mirror.func, dim3(mirror_grid), dim3(mirror.block),
                           args, 0, stream);

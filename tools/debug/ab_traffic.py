@@ -1,7 +1,7 @@
 """Per-launch HBM bytes (FETCH_SIZE x 2 + WRITE_SIZE, the gfx950 correction of
 tools/probes/summarize_profiles.py) of the gridder / degridder from the
-rocprofv3 --pmc databases an A/B script wrote (tools/debug/r05_s64_ab.sh,
-r05_nt_ab.sh): python tools/debug/ab_traffic.py DIR LIB [LIB ...]"""
+rocprofv3 --pmc databases an A/B script wrote (DIR/<LIB>_FETCH_SIZE and
+DIR/<LIB>_WRITE_SIZE): python tools/debug/ab_traffic.py DIR LIB [LIB ...]"""
 import glob
 import os
 import sys

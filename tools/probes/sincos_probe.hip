@@ -11,7 +11,7 @@
 //   fast      __sinf/__cosf (v_mul 1/2pi + v_sin/v_cos, no range reduction)
 //   rev_hw    revolutions(x) (Dekker-split 1/2pi) + v_sin_f32/v_cos_f32
 //   anch_hw   anchored: A within +-2.5 rad, r = fma(x-A, 1/2pi, rev(A))
-//   rev_poly  revolutions(x) + quadrant polynomial (IDG_SINCOS_POLY)
+//   rev_poly  revolutions(x) + quadrant polynomial (namespace poly below)
 //   hw_small  v_sin/v_cos on r uniform in [-0.5, 0.5] (pure unit accuracy)
 #include <hip/hip_runtime.h>
 
