@@ -266,6 +266,138 @@ int idg_release_workspaces(void *stream, int all);
 
 const char *idg_last_error(void);
 
+/* ---- per-call launch options ----------------------------------------------
+ * Which kernels a call runs, chosen by the caller for that call instead of by
+ * the process environment.  Every field uses 0 for "unset": the environment
+ * variable of the same meaning if it is set (IDG_GRIDDER_IMPL,
+ * IDG_DEGRIDDER_IMPL, IDG_PREC, IDG_KERNEL_FORM, IDG_GRID_FFT), else the
+ * library's default -- what the entries without options do.  An explicit
+ * field wins over its variable.  A NULL pointer and a zero-filled struct with
+ * struct_size set are the same thing.
+ *
+ * struct_size = sizeof(idg_options_t) of the caller's header.  Fields beyond
+ * a smaller struct_size count as unset; a larger one is accepted while every
+ * byte past the fields known here is zero.  IDG_E_INVALID_ARGUMENT: a
+ * struct_size below the first field's end or not a multiple of 4, a non-zero
+ * byte past the known fields, an unknown enum value, a degridder_impl other
+ * than ENV / DEFAULT / SEQUENTIAL.  No reference counterpart: the reference
+ * has one kernel per direction. */
+#define IDG_IMPL_ENV 0        /* unset                                       */
+#define IDG_IMPL_DEFAULT 1    /* the MFMA kernels, whatever the environment  */
+#define IDG_IMPL_VALU 2       /* gridder: the VALU mirror path               */
+#define IDG_IMPL_SEQUENTIAL 3 /* the reference CPU path's rounding sequence  */
+#define IDG_IMPL_ORDERED 4    /* gridder: reference summation order          */
+#define IDG_IMPL_AUTO 5       /* gridder: ORDERED for the subgrids with
+                                 nr_timesteps * nr_channels > auto_threshold,
+                                 DEFAULT for the others, chosen on the device
+                                 per subgrid                 */
+
+#define IDG_PREC_SET 8u /* precision = IDG_PREC_SET | bits (bits 0..7 as
+                           idg_precision_options), so bits = 0 can be forced */
+
+#define IDG_FORM_ENV 0
+#define IDG_FORM_COMBINED 1 /* one kernel for every subgrid                  */
+#define IDG_FORM_SPLIT 2    /* mirror kernel + queue-fed general kernel      */
+
+#define IDG_FFT_FUSION_ENV 0
+#define IDG_FFT_FUSION_OFF 1 /* idg_gridder_fft_launch: two launches         */
+#define IDG_FFT_FUSION_ON 2  /* the FFT in the gridder's epilogue (S = 32)   */
+
+#define IDG_AUTO_THRESHOLD_DEFAULT 16384u
+
+typedef struct idg_options_t {
+  uint32_t struct_size;    /* sizeof(idg_options_t)                          */
+  uint32_t gridder_impl;   /* IDG_IMPL_*                                     */
+  uint32_t degridder_impl; /* IDG_IMPL_ENV / _DEFAULT / _SEQUENTIAL          */
+  uint32_t precision;      /* 0, or IDG_PREC_SET | bits                      */
+  uint32_t kernel_form;    /* IDG_FORM_*                                     */
+  uint32_t fft_fusion;     /* IDG_FFT_FUSION_*                               */
+  uint32_t auto_threshold; /* IDG_IMPL_AUTO; 0 = IDG_AUTO_THRESHOLD_DEFAULT  */
+} idg_options_t;
+
+/* The entries above with options; the entries above are these with NULL.
+ * Under IDG_IMPL_AUTO the launch stays asynchronous (the classification runs
+ * on the device), each selected subgrid is bit for bit the IDG_IMPL_ORDERED
+ * launch's and each other one the IDG_IMPL_DEFAULT launch's of the same
+ * kernel form; precision and kernel_form apply to the default pass and the
+ * FFT of idg_gridder_fft_launch_opts is a launch of its own. */
+int idg_c_run_gridder_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                           float image_size, float w_step_in_lambda,
+                           int nr_channels, int nr_stations,
+                           const idg_uvw_t *uvw, size_t uvw_rows,
+                           const float *wavenumbers,
+                           const idg_cfloat_t *visibilities,
+                           const float *spheroidal, const idg_cfloat_t *aterms,
+                           size_t aterm_slots, const idg_metadata_t *metadata,
+                           idg_cfloat_t *subgrids,
+                           const idg_options_t *options);
+
+int idg_c_run_degridder_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                             float image_size, float w_step_in_lambda,
+                             int nr_channels, int nr_stations,
+                             const idg_uvw_t *uvw, size_t uvw_rows,
+                             const float *wavenumbers,
+                             idg_cfloat_t *visibilities,
+                             const float *spheroidal,
+                             const idg_cfloat_t *aterms, size_t aterm_slots,
+                             const idg_metadata_t *metadata,
+                             const idg_cfloat_t *subgrids,
+                             const idg_options_t *options);
+
+int idg_gridder_launch_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                            float image_size, float w_step_in_lambda,
+                            int nr_channels, int nr_stations,
+                            const idg_uvw_t *uvw, const float *wavenumbers,
+                            const idg_cfloat_t *visibilities,
+                            const float *spheroidal,
+                            const idg_cfloat_t *aterms,
+                            const idg_metadata_t *metadata,
+                            idg_cfloat_t *subgrids, void *stream,
+                            const idg_options_t *options);
+
+int idg_degridder_launch_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                              float image_size, float w_step_in_lambda,
+                              int nr_channels, int nr_stations,
+                              const idg_uvw_t *uvw, const float *wavenumbers,
+                              idg_cfloat_t *visibilities,
+                              const float *spheroidal,
+                              const idg_cfloat_t *aterms,
+                              const idg_metadata_t *metadata,
+                              const idg_cfloat_t *subgrids, void *stream,
+                              const idg_options_t *options);
+
+int idg_gridder_fft_launch_opts(int nr_subgrids, int grid_size,
+                                int subgrid_size, float image_size,
+                                float w_step_in_lambda, int nr_channels,
+                                int nr_stations, const idg_uvw_t *uvw,
+                                const float *wavenumbers,
+                                const idg_cfloat_t *visibilities,
+                                const float *spheroidal,
+                                const idg_cfloat_t *aterms,
+                                const idg_metadata_t *metadata,
+                                idg_cfloat_t *subgrids, void *stream,
+                                const idg_options_t *options);
+
+/* NULL (and idg_last_error) on invalid options.  Under IDG_IMPL_AUTO the
+ * gridder's name is gridder_auto_mi355x_{s32,s64,generic}. */
+const char *idg_kernel_name_opts(int direction, int subgrid_size,
+                                 int nr_channels,
+                                 const idg_options_t *options);
+
+/* < 0 on invalid options.  Under IDG_IMPL_AUTO: the default pass's bits. */
+int idg_precision_options_opts(int direction, int subgrid_size,
+                               int nr_channels, const idg_options_t *options);
+
+/* The host twin of IDG_IMPL_AUTO's device classification: selected[s] = 1 for
+ * every subgrid an auto launch with these options sends to the ordered
+ * kernel (nr_timesteps * nr_channels > the threshold, the product in 64
+ * bits; nr_timesteps <= 0 never), else 0; returns their count, < 0 on bad
+ * arguments.  metadata and selected are host pointers (selected may be NULL
+ * to count only). */
+int idg_auto_selected(int nr_subgrids, int nr_channels,
+                      const idg_options_t *options,
+                      const idg_metadata_t *metadata, uint8_t *selected);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,74 @@ idg_mi355x::Problem make_problem(int nr_subgrids, int grid_size,
   return p;
 }
 
+// idg_options_t -> idg_mi355x::Options (still a request: unset fields are
+// resolved from the environment where they are used).  The struct_size rules
+// of include/idg_mi355x.h.
+int parse_options(const idg_options_t *o, idg_mi355x::Options *out) {
+  *out = idg_mi355x::Options();
+  if (o == nullptr) return IDG_OK;
+  const uint32_t size = o->struct_size;
+  if (size < sizeof(uint32_t) || size % 4 != 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_options_t: struct_size " + std::to_string(size) +
+                    " (set it to sizeof(idg_options_t), a multiple of 4)");
+  if (size > (1u << 16))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_options_t: struct_size " + std::to_string(size) +
+                    " is no idg_options_t of any version");
+  // the caller's fields, zero-extended to this library's struct; bytes of a
+  // newer, larger struct must be zero (an option this library cannot honour)
+  idg_options_t v;
+  std::memset(&v, 0, sizeof v);
+  std::memcpy(&v, o, std::min<size_t>(size, sizeof v));
+  const unsigned char *raw = reinterpret_cast<const unsigned char *>(o);
+  for (size_t i = sizeof v; i < size; ++i)
+    if (raw[i] != 0)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "idg_options_t: struct_size " + std::to_string(size) +
+                      " with a field set that this library (struct_size " +
+                      std::to_string(sizeof v) + ") does not know");
+  if (v.gridder_impl > IDG_IMPL_AUTO)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_options_t: unknown gridder_impl " +
+                    std::to_string(v.gridder_impl));
+  if (v.degridder_impl != IDG_IMPL_ENV && v.degridder_impl != IDG_IMPL_DEFAULT &&
+      v.degridder_impl != IDG_IMPL_SEQUENTIAL)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_options_t: degridder_impl " +
+                    std::to_string(v.degridder_impl) +
+                    " (IDG_IMPL_DEFAULT or IDG_IMPL_SEQUENTIAL)");
+  if (v.precision != 0 && (v.precision & ~7u) != IDG_PREC_SET)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_options_t: precision " + std::to_string(v.precision) +
+                    " (0, or IDG_PREC_SET | bits 0..7)");
+  if (v.kernel_form > IDG_FORM_SPLIT)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_options_t: unknown kernel_form " +
+                                            std::to_string(v.kernel_form));
+  if (v.fft_fusion > IDG_FFT_FUSION_ON)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_options_t: unknown fft_fusion " +
+                                            std::to_string(v.fft_fusion));
+  out->gridder_impl = static_cast<int>(v.gridder_impl);
+  out->degridder_impl = static_cast<int>(v.degridder_impl);
+  out->precision = static_cast<int>(v.precision);
+  out->kernel_form = static_cast<int>(v.kernel_form);
+  out->fft_fusion = static_cast<int>(v.fft_fusion);
+  out->auto_threshold = v.auto_threshold;
+  return IDG_OK;
+}
+static_assert(IDG_IMPL_DEFAULT == idg_mi355x::kImplDefault &&
+                  IDG_IMPL_VALU == idg_mi355x::kImplValu &&
+                  IDG_IMPL_SEQUENTIAL == idg_mi355x::kImplSequential &&
+                  IDG_IMPL_ORDERED == idg_mi355x::kImplOrdered &&
+                  IDG_IMPL_AUTO == idg_mi355x::kImplAuto &&
+                  IDG_PREC_SET == idg_mi355x::kPrecSet &&
+                  IDG_FORM_COMBINED == idg_mi355x::kFormCombined &&
+                  IDG_FORM_SPLIT == idg_mi355x::kFormSplit &&
+                  IDG_FFT_FUSION_OFF == idg_mi355x::kFftFusionOff &&
+                  IDG_FFT_FUSION_ON == idg_mi355x::kFftFusionOn &&
+                  IDG_AUTO_THRESHOLD_DEFAULT == idg_mi355x::kAutoThreshold,
+              "idg_options_t values are idg_mi355x::Options values");
+
 int check_geometry(const idg_mi355x::Problem &p) {
   if (p.nr_subgrids < 0 || p.subgrid_size <= 0 || p.nr_channels <= 0 ||
       p.nr_stations <= 0)
@@ -60,7 +128,10 @@ int check_geometry(const idg_mi355x::Problem &p) {
 int run_host(idg_mi355x::Direction dir, const idg_mi355x::Problem &p,
              size_t uvw_rows, size_t aterm_slots, const void *uvw,
              const float *wn, void *vis, const float *sph, const void *at,
-             const idg_metadata_t *md, void *sg) {
+             const idg_metadata_t *md, void *sg,
+             const idg_options_t *options) {
+  idg_mi355x::Options opt;
+  if (int rc = parse_options(options, &opt)) return rc;
   if (int rc = check_geometry(p)) return rc;
   if (p.nr_subgrids == 0) return IDG_OK;
   if (!uvw || !wn || !vis || !sph || !at || !md || !sg)
@@ -71,7 +142,7 @@ int run_host(idg_mi355x::Direction dir, const idg_mi355x::Problem &p,
   std::string msg;
   const hipError_t err = idg_mi355x::run_host(
       dir, p, e, uvw, wn, vis, sph, at,
-      reinterpret_cast<const idg::Metadata *>(md), sg, &msg);
+      reinterpret_cast<const idg::Metadata *>(md), sg, &msg, nullptr, opt);
   if (!msg.empty()) return fail(IDG_E_OUT_OF_BOUNDS, msg);
   return from_hip(err, dir == idg_mi355x::Direction::kGridder
                            ? "idg_c_run_gridder"
@@ -80,14 +151,17 @@ int run_host(idg_mi355x::Direction dir, const idg_mi355x::Problem &p,
 
 int launch(idg_mi355x::Direction dir, const idg_mi355x::Problem &p,
            const void *uvw, const float *wn, void *vis, const float *sph,
-           const void *at, const void *md, void *sg, void *stream) {
+           const void *at, const void *md, void *sg, void *stream,
+           const idg_options_t *options) {
+  idg_mi355x::Options opt;
+  if (int rc = parse_options(options, &opt)) return rc;
   if (int rc = check_geometry(p)) return rc;
   if (p.nr_subgrids == 0) return IDG_OK;
   if (!uvw || !wn || !vis || !sph || !at || !md || !sg)
     return fail(IDG_E_INVALID_ARGUMENT, "null buffer");
   return from_hip(
       idg_mi355x::launch(dir, p, uvw, wn, vis, sph, at, md, sg,
-                         static_cast<hipStream_t>(stream)),
+                         static_cast<hipStream_t>(stream), nullptr, opt),
       "hipLaunchKernel");
 }
 
@@ -171,12 +245,29 @@ int idg_c_run_gridder(int nr_subgrids, int grid_size, int subgrid_size,
                       const float *spheroidal, const idg_cfloat_t *aterms,
                       size_t aterm_slots, const idg_metadata_t *metadata,
                       idg_cfloat_t *subgrids) {
+  return idg_c_run_gridder_opts(nr_subgrids, grid_size, subgrid_size,
+                                image_size, w_step_in_lambda, nr_channels,
+                                nr_stations, uvw, uvw_rows, wavenumbers,
+                                visibilities, spheroidal, aterms, aterm_slots,
+                                metadata, subgrids, nullptr);
+}
+
+int idg_c_run_gridder_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                           float image_size, float w_step_in_lambda,
+                           int nr_channels, int nr_stations,
+                           const idg_uvw_t *uvw, size_t uvw_rows,
+                           const float *wavenumbers,
+                           const idg_cfloat_t *visibilities,
+                           const float *spheroidal, const idg_cfloat_t *aterms,
+                           size_t aterm_slots, const idg_metadata_t *metadata,
+                           idg_cfloat_t *subgrids,
+                           const idg_options_t *options) {
   const auto p = make_problem(nr_subgrids, grid_size, subgrid_size,
                               image_size, w_step_in_lambda, nr_channels,
                               nr_stations);
   return run_host(idg_mi355x::Direction::kGridder, p, uvw_rows, aterm_slots,
                   uvw, wavenumbers, const_cast<idg_cfloat_t *>(visibilities),
-                  spheroidal, aterms, metadata, subgrids);
+                  spheroidal, aterms, metadata, subgrids, options);
 }
 
 int idg_c_run_degridder(int nr_subgrids, int grid_size, int subgrid_size,
@@ -187,12 +278,31 @@ int idg_c_run_degridder(int nr_subgrids, int grid_size, int subgrid_size,
                         const float *spheroidal, const idg_cfloat_t *aterms,
                         size_t aterm_slots, const idg_metadata_t *metadata,
                         const idg_cfloat_t *subgrids) {
+  return idg_c_run_degridder_opts(nr_subgrids, grid_size, subgrid_size,
+                                  image_size, w_step_in_lambda, nr_channels,
+                                  nr_stations, uvw, uvw_rows, wavenumbers,
+                                  visibilities, spheroidal, aterms,
+                                  aterm_slots, metadata, subgrids, nullptr);
+}
+
+int idg_c_run_degridder_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                             float image_size, float w_step_in_lambda,
+                             int nr_channels, int nr_stations,
+                             const idg_uvw_t *uvw, size_t uvw_rows,
+                             const float *wavenumbers,
+                             idg_cfloat_t *visibilities,
+                             const float *spheroidal,
+                             const idg_cfloat_t *aterms, size_t aterm_slots,
+                             const idg_metadata_t *metadata,
+                             const idg_cfloat_t *subgrids,
+                             const idg_options_t *options) {
   const auto p = make_problem(nr_subgrids, grid_size, subgrid_size,
                               image_size, w_step_in_lambda, nr_channels,
                               nr_stations);
   return run_host(idg_mi355x::Direction::kDegridder, p, uvw_rows,
                   aterm_slots, uvw, wavenumbers, visibilities, spheroidal,
-                  aterms, metadata, const_cast<idg_cfloat_t *>(subgrids));
+                  aterms, metadata, const_cast<idg_cfloat_t *>(subgrids),
+                  options);
 }
 
 int idg_gridder_launch(int nr_subgrids, int grid_size, int subgrid_size,
@@ -203,12 +313,29 @@ int idg_gridder_launch(int nr_subgrids, int grid_size, int subgrid_size,
                        const float *spheroidal, const idg_cfloat_t *aterms,
                        const idg_metadata_t *metadata, idg_cfloat_t *subgrids,
                        void *stream) {
+  return idg_gridder_launch_opts(nr_subgrids, grid_size, subgrid_size,
+                                 image_size, w_step_in_lambda, nr_channels,
+                                 nr_stations, uvw, wavenumbers, visibilities,
+                                 spheroidal, aterms, metadata, subgrids,
+                                 stream, nullptr);
+}
+
+int idg_gridder_launch_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                            float image_size, float w_step_in_lambda,
+                            int nr_channels, int nr_stations,
+                            const idg_uvw_t *uvw, const float *wavenumbers,
+                            const idg_cfloat_t *visibilities,
+                            const float *spheroidal,
+                            const idg_cfloat_t *aterms,
+                            const idg_metadata_t *metadata,
+                            idg_cfloat_t *subgrids, void *stream,
+                            const idg_options_t *options) {
   const auto p = make_problem(nr_subgrids, grid_size, subgrid_size,
                               image_size, w_step_in_lambda, nr_channels,
                               nr_stations);
   return launch(idg_mi355x::Direction::kGridder, p, uvw, wavenumbers,
                 const_cast<idg_cfloat_t *>(visibilities), spheroidal, aterms,
-                metadata, subgrids, stream);
+                metadata, subgrids, stream, options);
 }
 
 int idg_gridder_fft_launch(int nr_subgrids, int grid_size, int subgrid_size,
@@ -219,6 +346,24 @@ int idg_gridder_fft_launch(int nr_subgrids, int grid_size, int subgrid_size,
                            const float *spheroidal, const idg_cfloat_t *aterms,
                            const idg_metadata_t *metadata,
                            idg_cfloat_t *subgrids, void *stream) {
+  return idg_gridder_fft_launch_opts(nr_subgrids, grid_size, subgrid_size,
+                                     image_size, w_step_in_lambda, nr_channels,
+                                     nr_stations, uvw, wavenumbers,
+                                     visibilities, spheroidal, aterms,
+                                     metadata, subgrids, stream, nullptr);
+}
+
+int idg_gridder_fft_launch_opts(int nr_subgrids, int grid_size,
+                                int subgrid_size, float image_size,
+                                float w_step_in_lambda, int nr_channels,
+                                int nr_stations, const idg_uvw_t *uvw,
+                                const float *wavenumbers,
+                                const idg_cfloat_t *visibilities,
+                                const float *spheroidal,
+                                const idg_cfloat_t *aterms,
+                                const idg_metadata_t *metadata,
+                                idg_cfloat_t *subgrids, void *stream,
+                                const idg_options_t *options) {
   if (subgrid_size > 64)
     return fail(IDG_E_INVALID_ARGUMENT,
                 "idg_gridder_fft_launch: subgrid_size <= 64 (the FFT's)");
@@ -227,7 +372,7 @@ int idg_gridder_fft_launch(int nr_subgrids, int grid_size, int subgrid_size,
   p.fft_out = true;
   return launch(idg_mi355x::Direction::kGridder, p, uvw, wavenumbers,
                 const_cast<idg_cfloat_t *>(visibilities), spheroidal, aterms,
-                metadata, subgrids, stream);
+                metadata, subgrids, stream, options);
 }
 
 int idg_degridder_launch(int nr_subgrids, int grid_size, int subgrid_size,
@@ -238,12 +383,29 @@ int idg_degridder_launch(int nr_subgrids, int grid_size, int subgrid_size,
                          const idg_cfloat_t *aterms,
                          const idg_metadata_t *metadata,
                          const idg_cfloat_t *subgrids, void *stream) {
+  return idg_degridder_launch_opts(nr_subgrids, grid_size, subgrid_size,
+                                   image_size, w_step_in_lambda, nr_channels,
+                                   nr_stations, uvw, wavenumbers, visibilities,
+                                   spheroidal, aterms, metadata, subgrids,
+                                   stream, nullptr);
+}
+
+int idg_degridder_launch_opts(int nr_subgrids, int grid_size, int subgrid_size,
+                              float image_size, float w_step_in_lambda,
+                              int nr_channels, int nr_stations,
+                              const idg_uvw_t *uvw, const float *wavenumbers,
+                              idg_cfloat_t *visibilities,
+                              const float *spheroidal,
+                              const idg_cfloat_t *aterms,
+                              const idg_metadata_t *metadata,
+                              const idg_cfloat_t *subgrids, void *stream,
+                              const idg_options_t *options) {
   const auto p = make_problem(nr_subgrids, grid_size, subgrid_size,
                               image_size, w_step_in_lambda, nr_channels,
                               nr_stations);
   return launch(idg_mi355x::Direction::kDegridder, p, uvw, wavenumbers,
                 visibilities, spheroidal, aterms, metadata,
-                const_cast<idg_cfloat_t *>(subgrids), stream);
+                const_cast<idg_cfloat_t *>(subgrids), stream, options);
 }
 
 int idg_validate_metadata(int nr_subgrids, int subgrid_size, int nr_channels,
@@ -279,19 +441,57 @@ int idg_host_chunk_plan(int nr_subgrids, const idg_metadata_t *metadata,
 }
 
 const char *idg_kernel_name(int direction, int subgrid_size, int nr_channels) {
+  return idg_kernel_name_opts(direction, subgrid_size, nr_channels, nullptr);
+}
+
+const char *idg_kernel_name_opts(int direction, int subgrid_size,
+                                 int nr_channels,
+                                 const idg_options_t *options) {
+  idg_mi355x::Options opt;
+  if (parse_options(options, &opt)) return nullptr;
   idg_mi355x::Problem p;
   p.subgrid_size = subgrid_size;
   p.nr_channels = nr_channels;
-  return direction == 0 ? idg_mi355x::select_gridder(p).name
-                        : idg_mi355x::select_degridder(p).name;
+  return direction == 0 ? idg_mi355x::select_gridder(p, opt).name
+                        : idg_mi355x::select_degridder(p, opt).name;
 }
 
 int idg_precision_options(int direction, int subgrid_size, int nr_channels) {
+  return idg_precision_options_opts(direction, subgrid_size, nr_channels,
+                                    nullptr);
+}
+
+int idg_precision_options_opts(int direction, int subgrid_size,
+                               int nr_channels, const idg_options_t *options) {
+  idg_mi355x::Options opt;
+  if (int rc = parse_options(options, &opt)) return rc;
   idg_mi355x::Problem p;
   p.subgrid_size = subgrid_size;
   p.nr_channels = nr_channels;
-  return direction == 0 ? idg_mi355x::select_gridder(p).prec
-                        : idg_mi355x::select_degridder(p).prec;
+  return direction == 0 ? idg_mi355x::select_gridder(p, opt).prec
+                        : idg_mi355x::select_degridder(p, opt).prec;
+}
+
+int idg_auto_selected(int nr_subgrids, int nr_channels,
+                      const idg_options_t *options,
+                      const idg_metadata_t *metadata, uint8_t *selected) {
+  idg_mi355x::Options opt;
+  if (int rc = parse_options(options, &opt)) return rc;
+  if (nr_subgrids < 0 || nr_channels <= 0 ||
+      (nr_subgrids > 0 && metadata == nullptr))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_auto_selected: nr_subgrids >= 0, nr_channels > 0 and "
+                "metadata required");
+  const unsigned threshold =
+      idg_mi355x::resolve_options(opt).auto_threshold;
+  int count = 0;
+  for (int s = 0; s < nr_subgrids; ++s) {
+    const bool sel = idg_mi355x::auto_selects(metadata[s].nr_timesteps,
+                                              nr_channels, threshold);
+    if (selected) selected[s] = sel ? 1 : 0;
+    count += sel ? 1 : 0;
+  }
+  return count;
 }
 
 double idg_p_run_gridder(void) {

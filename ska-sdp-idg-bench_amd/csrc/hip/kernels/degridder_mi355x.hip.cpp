@@ -868,17 +868,14 @@ DegridderSet degridder_set_for(bool nw8, bool tail) {
   return tail ? degridder_set<S_, 4, true>() : degridder_set<S_, 4, false>();
 }
 
-// IDG_DEGRIDDER_IMPL=valu selects the VALU mirror path (A/B comparisons).
-static int degridder_impl() {
-  const char *v = std::getenv("IDG_DEGRIDDER_IMPL");
-  if (v && std::string(v) == "sequential") return 2;
-  return (v && std::string(v) == "valu") ? 0 : 1;
-}
-
-KernelChoice select_degridder(const Problem &p) {
+// Options::degridder_impl (util.hpp; IDG_DEGRIDDER_IMPL where the caller left
+// it unset): kImplValu the VALU mirror path (A/B comparisons, by environment
+// only), kImplSequential the order-preserving kernel.
+KernelChoice select_degridder(const Problem &p, const Options &request) {
+  const Options opt = resolve_options(request);
   KernelChoice k;
   k.grid = p.nr_subgrids;
-  if (degridder_impl() == 2) {  // bit-exact to the reference's CPU output
+  if (opt.degridder_impl == kImplSequential) {  // bit-exact to the reference's CPU output
     k.func = sequential_degridder(p.subgrid_size);
     k.block = sequential_block();
     k.name = p.subgrid_size == 32   ? "degridder_sequential_mi355x_s32"
@@ -890,7 +887,7 @@ KernelChoice select_degridder(const Problem &p) {
   const int C = p.nr_channels;
   const bool cg8 = C % 8 == 0 || (C % 4 != 0 && C >= 8);
   const bool s32 = p.subgrid_size == 32, s64 = p.subgrid_size == 64;
-  const bool mfma = degridder_impl() == 1;
+  const bool mfma = opt.degridder_impl != kImplValu;
   // Small launches (a shard of the batch: 3,063 subgrids at N = 8) take
   // 8-wave workgroups: half the workgroup duration, so half the drain of
   // the last round (0.926 vs 0.935 ms at 3,063 subgrids); large ones keep
@@ -901,7 +898,7 @@ KernelChoice select_degridder(const Problem &p) {
   if (const char *v = std::getenv("IDG_DEGRID_NW"))
     nw8 = mfma && std::string(v) == "8";
   if (mfma) {
-    k.prec = precision_for(Direction::kDegridder, p);
+    k.prec = precision_for(Direction::kDegridder, p, opt);
     const bool tail = (k.prec & kPrecTail) != 0;
     const DegridderSet set = s32   ? degridder_set_for<32>(nw8, tail)
                              : s64 ? degridder_set_for<64>(nw8, tail)
@@ -909,7 +906,7 @@ KernelChoice select_degridder(const Problem &p) {
     // the MFMA kernel has no CG
     k.func = set.combined;
     k.block = nw8 ? 512 : 256;
-    if (two_kernel_form(p.nr_subgrids)) {
+    if (two_kernel_form(p.nr_subgrids, opt)) {
       // mirror-eligible subgrids (even S only), then the others on 8-wave
       // workgroups with 1,024-pixel chunks
       if (s64)  // 8 waves, 1,024-pair chunks

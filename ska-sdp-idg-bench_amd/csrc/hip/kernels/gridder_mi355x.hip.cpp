@@ -1383,22 +1383,18 @@ GridderSet gridder_set_for(int prec) {
   reinterpret_cast<const void *>(                                         \
       &kernel_gridder_mi355x<S_, PPT_, 16, 0, IDG_GRID_PT>)
 
-// IDG_GRIDDER_IMPL=valu selects the VALU mirror path (A/B comparisons);
-// IDG_GRIDDER_IMPL=sequential the order-preserving kernel, bit-exact to the
-// reference's CPU output (sequential_mi355x.hip.cpp); IDG_GRIDDER_IMPL=
-// ordered the reference's summation order with the hardware sin / cos
-// (ordered_mi355x.hip.cpp).
-static int gridder_impl() {
-  const char *v = std::getenv("IDG_GRIDDER_IMPL");
-  if (v && std::string(v) == "sequential") return 2;
-  if (v && std::string(v) == "ordered") return 3;
-  return (v && std::string(v) == "valu") ? 0 : 1;
-}
-
-KernelChoice select_gridder(const Problem &p) {
+// Options::gridder_impl (util.hpp; IDG_GRIDDER_IMPL where the caller left it
+// unset): kImplValu the VALU mirror path (A/B comparisons); kImplSequential
+// the order-preserving kernel, bit-exact to the reference's CPU output
+// (sequential_mi355x.hip.cpp); kImplOrdered the reference's summation order
+// with the hardware sin / cos (ordered_mi355x.hip.cpp); kImplAuto the MFMA
+// kernels below as the default pass of the auto gridder (util.cpp launch).
+KernelChoice select_gridder(const Problem &p, const Options &request) {
+  const Options opt = resolve_options(request);
+  const int impl = opt.gridder_impl;
   KernelChoice k;
   k.grid = p.nr_subgrids;
-  if (gridder_impl() == 2) {
+  if (impl == kImplSequential) {
     k.func = sequential_gridder(p.subgrid_size);
     k.block = sequential_block();
     k.name = p.subgrid_size == 32   ? "gridder_sequential_mi355x_s32"
@@ -1406,7 +1402,7 @@ KernelChoice select_gridder(const Problem &p) {
                                     : "gridder_sequential_mi355x_generic";
     return k;  // no FFT epilogue: launch() runs launch_subgrid_fft after it
   }
-  if (gridder_impl() == 3) {  // one combined launch, k.prec = 0, no epilogue
+  if (impl == kImplOrdered) {  // one combined launch, k.prec = 0, no epilogue
     k.func = ordered_gridder(p.subgrid_size);
     k.block = ordered_block();
     k.name = p.subgrid_size == 32   ? "gridder_ordered_mi355x_s32"
@@ -1414,21 +1410,24 @@ KernelChoice select_gridder(const Problem &p) {
                                     : "gridder_ordered_mi355x_generic";
     return k;
   }
-  const bool mfma = gridder_impl() == 1;
+  const bool mfma = impl != kImplValu;
+  const bool auto_ordered = impl == kImplAuto;
+  k.auto_ordered = auto_ordered;
+  k.auto_threshold = opt.auto_threshold;
   k.block = mfma ? 64 * IDG_GRID_NW : kBlock;
   // the options the selected kernel is built with (reported by
   // idg_precision_options / bench.py): the alternating tail replaces the
   // every-phasor one, blocked summation exists at S = 32 only, and the VALU
   // kernel has none of them
-  k.prec = precision_for(Direction::kGridder, p);
+  k.prec = precision_for(Direction::kGridder, p, opt);
   if (k.prec & kPrecTailAlt) k.prec &= ~kPrecTail;
   if (p.subgrid_size != 32) k.prec &= ~kPrecFlush;
   if (!mfma) k.prec = 0;
-  // the FFT in the gridder's epilogue (S = 32, MFMA; IDG_GRID_FFT=0: the
-  // launch layer runs launch_subgrid_fft after the plain gridder instead)
-  const char *fenv = std::getenv("IDG_GRID_FFT");
+  // the FFT in the gridder's epilogue (S = 32, MFMA; fusion off, or auto,
+  // whose ordered pass writes image-domain subgrids: the launch layer runs
+  // launch_subgrid_fft after the gridder instead)
   const bool fft_epilogue = p.fft_out && mfma && p.subgrid_size == 32 &&
-                            !(fenv != nullptr && fenv[0] == '0');
+                            !auto_ordered && opt.fft_fusion != kFftFusionOff;
   GridderSet set{};
   switch (p.subgrid_size) {
     case 32:
@@ -1454,7 +1453,11 @@ KernelChoice select_gridder(const Problem &p) {
       break;
   }
   k.func = set.combined;
-  if (mfma && two_kernel_form(p.nr_subgrids)) {
+  if (auto_ordered)
+    k.name = p.subgrid_size == 32   ? "gridder_auto_mi355x_s32"
+             : p.subgrid_size == 64 ? "gridder_auto_mi355x_s64"
+                                    : "gridder_auto_mi355x_generic";
+  if (mfma && two_kernel_form(p.nr_subgrids, opt)) {
     if (set.mirror)
       k.parts[0] = {set.mirror, k.block, KernelChoice::kMirror,
                     mirror_split(p.subgrid_size)};

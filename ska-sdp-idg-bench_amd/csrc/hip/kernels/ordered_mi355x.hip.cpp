@@ -24,9 +24,10 @@
 // per phasor: the MFMA kernels' anchored / incremental reduction rounds the
 // phase differently and is not used here.
 //
-// Selected by IDG_GRIDDER_IMPL=ordered (read per call, util.hpp
-// select_gridder); the 13-argument kernel ABI, grid = nr_subgrids, block =
-// 256.  Layout of the work as the sequential gridder: a lane owns pixels
+// Selected by Options::gridder_impl = kImplOrdered (IDG_GRIDDER_IMPL=ordered;
+// util.hpp select_gridder); the 13-argument kernel ABI, grid = nr_subgrids,
+// block = 256.  The auto gridder's queue-fed variant is at the end of this
+// file.  Layout of the work as the sequential gridder: a lane owns pixels
 // whole (8 f32 accumulators each), the visibilities and (u, v, w, k) come
 // through LDS kSeqStage (t, c) items at a time, and on mirror subgrids (even
 // S, w = 0 and w_offset = 0) pixel npix-1-p takes the base pixel's phasor
@@ -34,6 +35,8 @@
 // phase -- checked per phasor; where it is not, the mirror's own phasor is
 // evaluated.  No sincosf tables: the LDS holds the staged block only.
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
 
 #include "../util.hpp"
 #include "device.hpp"
@@ -207,5 +210,163 @@ const void *ordered_gridder(int S) {
 }
 
 int ordered_block() { return kSeqBlock; }
+
+// ---------------------------------------------------------------------------
+// The auto gridder's two kernels (util.hpp launch_auto_classify /
+// launch_ordered_queue).  Workspace, in ints: [0] the count
+// of queued subgrids (zeroed by a memset before the classification), [16,
+// 16 + ns) the queue, then the shadow metadata (ns records).
+// ---------------------------------------------------------------------------
+namespace {
+constexpr int kAutoQueue = 16;  // the count has a 64-byte line of its own
+constexpr int kClassifyBlock = 256;
+}  // namespace
+
+size_t auto_workspace_bytes(int ns) {
+  return (kAutoQueue + static_cast<size_t>(ns)) * sizeof(int) +
+         static_cast<size_t>(ns) * sizeof(idg::Metadata);
+}
+
+const void *auto_shadow(void *ws, int ns) {
+  return static_cast<int *>(ws) + kAutoQueue + ns;
+}
+
+// One thread per subgrid.  A wave's pushes take one atomic (a count per push
+// serializes: device.hpp, the queue of the two-kernel form); the queue's
+// order is therefore not fixed from launch to launch, which no output
+// depends on: a queue position only names the subgrid a workgroup computes.
+__global__ void __launch_bounds__(kClassifyBlock)
+    kernel_auto_classify_mi355x(int nr_subgrids, int nr_channels,
+                                unsigned threshold,
+                                const idg::Metadata *__restrict__ metadata,
+                                int *__restrict__ ws) {
+  // a record as its 9 ints (nr_timesteps is the third), kept in registers
+  constexpr int kWords = sizeof(idg::Metadata) / sizeof(int);
+  static_assert(sizeof(idg::Metadata) == 36 &&
+                    offsetof(idg::Metadata, nr_timesteps) == 2 * sizeof(int),
+                "metadata layout");
+  const int s = blockIdx.x * kClassifyBlock + threadIdx.x;
+  const bool live = s < nr_subgrids;
+  const int *src = reinterpret_cast<const int *>(metadata) +
+                   static_cast<size_t>(live ? s : 0) * kWords;
+  int w[kWords];
+#pragma unroll
+  for (int i = 0; i < kWords; ++i) w[i] = src[i];
+  const bool selected =
+      live && w[2] > 0 &&
+      static_cast<long long>(w[2]) * nr_channels >
+          static_cast<long long>(threshold);
+  const unsigned long long mask = __ballot(selected);
+  const int lane = threadIdx.x & 63;
+  int first = 0;
+  if (lane == 0 && mask != 0) first = atomicAdd(ws, __popcll(mask));
+  first = __shfl(first, 0);
+  if (selected) {
+    ws[kAutoQueue + first + __popcll(mask & ((1ull << lane) - 1))] = s;
+    w[2] = 0;
+  }
+  if (!live) return;
+  int *dst = ws + kAutoQueue + nr_subgrids + static_cast<size_t>(s) * kWords;
+#pragma unroll
+  for (int i = 0; i < kWords; ++i) dst[i] = w[i];
+}
+
+// kernel_gridder_ordered_mi355x over the queue: workgroup b takes slice
+// b % slices of the subgrid at queue position b / slices and returns if that
+// is past the count.  A slice is a contiguous range of the base pixels (the
+// half subgrid on mirror subgrids, else all of it); a lane owns NPM base
+// pixels with their mirrors, or 2 NPM pixels (the ordered kernel: NPM = 2).
+// Every pixel's sum runs whole, in the same order, in one lane, and the
+// mirror check is per lane, so the output is the ordered kernel's bit for
+// bit whatever the slicing.  grid = nr_subgrids x slices.
+template <int S_CT, int NPM>
+__global__ void __launch_bounds__(kSeqBlock)
+    kernel_gridder_ordered_queue_mi355x(
+        const int grid_size, int subgrid_size, float image_size,
+        float w_step_in_lambda, int nr_channels, int nr_stations,
+        const idg::UVWCoordinate<float> *__restrict__ uvw,
+        const float *__restrict__ wavenumbers,
+        const float2 *__restrict__ visibilities,
+        const float *__restrict__ spheroidal,
+        const float2 *__restrict__ aterms,
+        const idg::Metadata *__restrict__ metadata,
+        float2 *__restrict__ subgrids, const int *__restrict__ ws,
+        int slices) {
+  __shared__ float4 st_vis[kSeqStage * 2];
+  __shared__ float4 st_uvwk[kSeqStage];
+  const int position = blockIdx.x / slices, slice = blockIdx.x % slices;
+  if (position >= ws[0]) return;
+  const int s = ws[kAutoQueue + position];
+  const int S = S_CT > 0 ? S_CT : subgrid_size;
+  const int npix = S * S;
+  const int tid = threadIdx.x;
+  const SubgridSetup g = setup_subgrid(metadata, s, grid_size, S, image_size,
+                                       w_step_in_lambda);
+  float2 *out = subgrids + static_cast<size_t>(s) * 4 * npix;
+  bool w_nonzero = false;
+  for (int t = tid; t < g.nr_timesteps; t += kSeqBlock)
+    w_nonzero |= uvw[g.time_offset + t].w != 0.0f;
+  const bool mirror = __syncthreads_or(w_nonzero) == 0 && S % 2 == 0 &&
+                      g.w_offset == 0.0f;
+  const int nbase = mirror ? npix / 2 : npix;
+  const int span = (nbase + slices - 1) / slices;
+  const int lo = slice * span, hi = min(nbase, lo + span);
+  if (mirror) {
+    constexpr int NP = NPM;
+    for (int tile = lo; tile < hi; tile += kSeqBlock * NP) {
+      int base[NP];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
+      ord_grid_pixels<NP, true>(base, hi, S, npix, image_size, g, nr_channels,
+                                nr_stations, uvw, wavenumbers, visibilities,
+                                spheroidal, aterms, out, st_vis, st_uvwk);
+    }
+    return;
+  }
+  constexpr int NP = 2 * NPM;
+  for (int tile = lo; tile < hi; tile += kSeqBlock * NP) {
+    int base[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
+    ord_grid_pixels<NP, false>(base, hi, S, npix, image_size, g, nr_channels,
+                               nr_stations, uvw, wavenumbers, visibilities,
+                               spheroidal, aterms, out, st_vis, st_uvwk);
+  }
+}
+
+hipError_t launch_auto_classify(int nr_subgrids, int nr_channels,
+                                unsigned threshold, const void *d_metadata,
+                                void *ws, hipStream_t stream) {
+  hipError_t err = hipMemsetAsync(ws, 0, sizeof(int), stream);
+  if (err != hipSuccess) return err;
+  void *args[] = {&nr_subgrids, &nr_channels, &threshold, &d_metadata, &ws};
+  return hipLaunchKernel(
+      reinterpret_cast<const void *>(&kernel_auto_classify_mi355x),
+      dim3((nr_subgrids + kClassifyBlock - 1) / kClassifyBlock),
+      dim3(kClassifyBlock), args, 0, stream);
+}
+
+hipError_t launch_ordered_queue(const Problem &p, void **args13, void *ws,
+                                int slices, hipStream_t stream) {
+  // whole pixels per lane: one slice keeps the ordered kernel's 2 (+ their
+  // mirrors), finer slicings take 1
+#define IDG_ORDERED_QUEUE(S_)                                              \
+  (slices > 1 ? reinterpret_cast<const void *>(                            \
+                    &kernel_gridder_ordered_queue_mi355x<S_, 1>)           \
+              : reinterpret_cast<const void *>(                            \
+                    &kernel_gridder_ordered_queue_mi355x<S_, 2>))
+  const void *func = p.subgrid_size == 32   ? IDG_ORDERED_QUEUE(32)
+                     : p.subgrid_size == 64 ? IDG_ORDERED_QUEUE(64)
+                                            : IDG_ORDERED_QUEUE(0);
+#undef IDG_ORDERED_QUEUE
+  void *args[15];
+  for (int i = 0; i < 13; ++i) args[i] = args13[i];
+  args[13] = &ws;
+  args[14] = &slices;
+  const long long grid = static_cast<long long>(p.nr_subgrids) * slices;
+  if (slices < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  return hipLaunchKernel(func, dim3(static_cast<unsigned>(grid)),
+                         dim3(kSeqBlock), args, 0, stream);
+}
 
 }  // namespace idg_mi355x

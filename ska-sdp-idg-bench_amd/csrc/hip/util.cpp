@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <iostream>
 #include <map>
 #include <mutex>
@@ -75,23 +76,14 @@ void print_dimensions(dim3 g, dim3 b) {
 }
 
 namespace {
-// The timed loop of p_run_kernel: one kernel per iteration, or the
-// two-kernel form of the MI355X kernels (util.hpp KernelChoice::parts).
-double time_launches(const idg_mi355x::KernelChoice &k, dim3 gridDim,
-                     void **args, const std::string &func_name, double gflops,
-                     double gbytes, double mvis) {
+// The timed loop of p_run_kernel: `once` enqueues one iteration on the
+// legacy default stream.
+double time_iterations(const std::function<void()> &once,
+                       const std::string &func_name, double gflops,
+                       double gbytes, double mvis) {
   const int warm = static_cast<int>(get_env_var("NR_WARM_UP_RUNS", 2));
   const int iters =
       std::max(1, static_cast<int>(get_env_var("NR_ITERATIONS", 5)));
-  auto once = [&] {
-    if (k.parts[1].func)
-      hipCheck(idg_mi355x::launch_parts(
-          k, static_cast<int>(gridDim.x), args,
-          *static_cast<float *>(args[3]) != 0.0f, nullptr));
-    else
-      hipCheck(hipLaunchKernel(k.func, gridDim, dim3(k.block), args, 0,
-                               nullptr));
-  };
   hipEvent_t start, stop;
   hipCheck(hipEventCreate(&start));
   hipCheck(hipEventCreate(&stop));
@@ -110,6 +102,24 @@ double time_launches(const idg_mi355x::KernelChoice &k, dim3 gridDim,
   report_csv(func_name, get_device_name(), "-hip.csv", seconds, gflops, gbytes,
              mvis);
   return seconds;
+}
+
+// One kernel per iteration, or the two-kernel form of the MI355X kernels
+// (util.hpp KernelChoice::parts).
+double time_launches(const idg_mi355x::KernelChoice &k, dim3 gridDim,
+                     void **args, const std::string &func_name, double gflops,
+                     double gbytes, double mvis) {
+  return time_iterations(
+      [&] {
+        if (k.parts[1].func)
+          hipCheck(idg_mi355x::launch_parts(
+              k, static_cast<int>(gridDim.x), args,
+              *static_cast<float *>(args[3]) != 0.0f, nullptr));
+        else
+          hipCheck(hipLaunchKernel(k.func, gridDim, dim3(k.block), args, 0,
+                                   nullptr));
+      },
+      func_name, gflops, gbytes, mvis);
 }
 }  // namespace
 
@@ -224,15 +234,65 @@ void print_benchmark() {
 
 namespace idg_mi355x {
 
-bool two_kernel_form(int nr_subgrids) {
-  const char *v = std::getenv("IDG_KERNEL_FORM");
-  if (v != nullptr && std::string(v) == "combined") return false;
-  if (v != nullptr && std::string(v) == "split") return true;
+// The one reader of the mode variables: a field the caller left unset takes
+// its variable's value, else the library's default.
+Options resolve_options(const Options &request) {
+  if (request.resolved) return request;
+  Options o = request;
+  const auto env = [](const char *name) {
+    const char *v = std::getenv(name);
+    return std::string(v ? v : "");
+  };
+  if (o.gridder_impl == 0) {
+    // valu: the VALU mirror path (A/B comparisons); sequential: the
+    // order-preserving kernel, bit-exact to the reference's CPU output;
+    // ordered: the reference's summation order with the hardware sin / cos;
+    // auto: ordered per subgrid above auto_threshold, else the MFMA kernels
+    const std::string v = env("IDG_GRIDDER_IMPL");
+    o.gridder_impl = v == "sequential" ? kImplSequential
+                     : v == "ordered"  ? kImplOrdered
+                     : v == "auto"     ? kImplAuto
+                     : v == "valu"     ? kImplValu
+                                       : kImplDefault;
+  }
+  if (o.degridder_impl == 0) {
+    const std::string v = env("IDG_DEGRIDDER_IMPL");
+    o.degridder_impl = v == "sequential" ? kImplSequential
+                       : v == "valu"     ? kImplValu
+                                         : kImplDefault;
+  }
+  if (o.precision == 0)
+    if (const char *v = std::getenv("IDG_PREC"))
+      o.precision = kPrecSet | (std::atoi(v) & 7);
+  if (o.kernel_form == 0) {
+    const std::string v = env("IDG_KERNEL_FORM");
+    o.kernel_form = v == "combined" ? kFormCombined
+                    : v == "split"  ? kFormSplit
+                                    : kFormBySize;
+  }
+  if (o.fft_fusion == 0)
+    o.fft_fusion = env("IDG_GRID_FFT")[0] == '0' ? kFftFusionOff : kFftFusionOn;
+  if (o.auto_threshold == 0) o.auto_threshold = kAutoThreshold;
+  o.resolved = true;
+  return o;
+}
+
+bool two_kernel_form(int nr_subgrids, const Options &opt) {
+  const int form = resolve_options(opt).kernel_form;
+  if (form == kFormCombined) return false;
+  if (form == kFormSplit) return true;
   return nr_subgrids >= kTwoKernelMinLaunch;
 }
 
-int precision_for(Direction dir, const Problem &p) {
-  if (const char *v = std::getenv("IDG_PREC")) return std::atoi(v) & 7;
+bool auto_selects(long long nr_timesteps, long long nr_channels,
+                  unsigned threshold) {
+  return nr_timesteps > 0 &&
+         nr_timesteps * nr_channels > static_cast<long long>(threshold);
+}
+
+int precision_for(Direction dir, const Problem &p, const Options &opt) {
+  const int forced = resolve_options(opt).precision;
+  if (forced & kPrecSet) return forced & 7;
   // degridder: no reduction tail (its visibilities are not coherent sums
   // over channels; measured 1.00e-6 vs 0.97e-6 from exact at the -c
   // defaults, 8.1e-7 vs 6.7e-7 at C = 256, for 5 % of its time)
@@ -287,12 +347,13 @@ hipError_t launch(Direction dir, const Problem &p, const void *d_uvw,
                   const float *d_wavenumbers, void *d_visibilities,
                   const float *d_spheroidal, const void *d_aterms,
                   const void *d_metadata, void *d_subgrids,
-                  hipStream_t stream, const KernelChoice *force) {
+                  hipStream_t stream, const KernelChoice *force,
+                  const Options &opt) {
   if (p.nr_subgrids <= 0) return hipSuccess;
   const KernelChoice k =
       force ? *force
-            : (dir == Direction::kGridder ? select_gridder(p)
-                                          : select_degridder(p));
+            : (dir == Direction::kGridder ? select_gridder(p, opt)
+                                          : select_degridder(p, opt));
   if (k.func == nullptr) return hipErrorInvalidConfiguration;
   int grid_size = p.grid_size, subgrid_size = p.subgrid_size;
   float image_size = p.image_size, w_step = p.w_step_in_lambda;
@@ -302,12 +363,37 @@ hipError_t launch(Direction dir, const Problem &p, const void *d_uvw,
                   &d_uvw,         &d_wavenumbers,   &d_visibilities,
                   &d_spheroidal,  &d_aterms,        &d_metadata,
                   &d_subgrids};
-  const hipError_t err =
-      (force || k.parts[1].func == nullptr)
-          ? hipLaunchKernel(k.func, dim3(p.nr_subgrids), dim3(k.block), args,
-                            0, stream)
-          : launch_parts(k, p.nr_subgrids, args, p.w_step_in_lambda != 0.0f,
-                         stream);
+  const auto default_pass = [&]() {
+    return (force || k.parts[1].func == nullptr)
+               ? hipLaunchKernel(k.func, dim3(p.nr_subgrids), dim3(k.block),
+                                 args, 0, stream)
+               : launch_parts(k, p.nr_subgrids, args,
+                              p.w_step_in_lambda != 0.0f, stream);
+  };
+  hipError_t err = hipSuccess;
+  if (k.auto_ordered) {
+    // classify on the device; the default kernels on the shadow metadata
+    // (selected subgrids empty: zeros); the ordered kernel over the queue on
+    // the true metadata.  Stream order alone separates the three.
+    WorkspaceLease lease;
+    err = lease.acquire(stream, kWorkspaceAuto,
+                        auto_workspace_bytes(p.nr_subgrids));
+    if (err != hipSuccess) return err;
+    err = launch_auto_classify(p.nr_subgrids, p.nr_channels, k.auto_threshold,
+                               d_metadata, lease.ptr, stream);
+    const void *true_metadata = d_metadata;
+    d_metadata = auto_shadow(lease.ptr, p.nr_subgrids);
+    if (err == hipSuccess) err = default_pass();
+    d_metadata = true_metadata;
+    int slices = kAutoSlices;
+    // IDG_AUTO_SLICES: the slicing A/B of tools/debug/auto_rate.py
+    if (const char *v = std::getenv("IDG_AUTO_SLICES"))
+      slices = std::max(1, std::min(64, std::atoi(v)));
+    if (err == hipSuccess)
+      err = launch_ordered_queue(p, args, lease.ptr, slices, stream);
+  } else {
+    err = default_pass();
+  }
   if (err != hipSuccess || dir != Direction::kGridder || !p.fft_out ||
       k.fft_in_kernel)
     return err;
@@ -584,7 +670,8 @@ hipError_t run_host(Direction dir, const Problem &p, const Extents &e,
                     void *visibilities, const float *spheroidal,
                     const void *aterms, const idg::Metadata *metadata,
                     void *subgrids, std::string *msg,
-                    const KernelChoice *force) {
+                    const KernelChoice *force, const Options &request) {
+  const Options opt = resolve_options(request);  // one read for every chunk
   const std::string bad = validate(p, e, metadata);
   if (!bad.empty()) {
     if (msg) *msg = bad;
@@ -702,7 +789,8 @@ hipError_t run_host(Direction dir, const Problem &p, const Extents &e,
                    static_cast<const float *>(d_wn.ptr), vis_d + delta * row_b,
                    static_cast<const float *>(d_sph.ptr), d_at.ptr,
                    static_cast<const idg::Metadata *>(d_md.ptr) + sb[i],
-                   sg_d + static_cast<size_t>(sb[i]) * sg_b, s_k.s, force);
+                   sg_d + static_cast<size_t>(sb[i]) * sg_b, s_k.s, force,
+                   opt);
     }
     if (err == hipSuccess) err = hipGetLastError();
     if (err == hipSuccess) err = hipEventRecord(e_k[i].e, s_k.s);
@@ -806,7 +894,16 @@ double run_performance(Direction dir, const void *func, std::string name,
   const KernelChoice k = dir == Direction::kGridder ? select_gridder(p)
                                                     : select_degridder(p);
   double seconds;
-  if (func == k.func && k.parts[1].func) {
+  if (func == k.func && k.auto_ordered) {
+    // the auto gridder (IDG_GRIDDER_IMPL=auto) is its launch sequence
+    seconds = hip::time_iterations(
+        [&] {
+          hipCheck(launch(dir, p, d_uvw, static_cast<const float *>(d_wn),
+                          d_vis, static_cast<const float *>(d_sph), d_at, d_md,
+                          d_sg, nullptr));
+        },
+        name, gflops, gbytes, mvis);
+  } else if (func == k.func && k.parts[1].func) {
     seconds = hip::time_launches(k, dim3(nr_subgrids), args, name, gflops,
                                  gbytes, mvis);
   } else {

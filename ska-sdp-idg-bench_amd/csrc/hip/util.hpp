@@ -104,6 +104,32 @@ struct Problem {
   bool fft_out = false;
 };
 
+// Which kernels one call runs (include/idg_mi355x.h idg_options_t, the same
+// numbers).  As a request every field may be 0 = unset; resolve_options()
+// fills the unset ones from the environment -- the only place IDG_GRIDDER_IMPL,
+// IDG_DEGRIDDER_IMPL, IDG_PREC, IDG_KERNEL_FORM and IDG_GRID_FFT are read --
+// and marks the value resolved.  A default-constructed Options is therefore
+// the environment route, which is what every entry without options takes.
+constexpr int kImplDefault = 1, kImplValu = 2, kImplSequential = 3,
+              kImplOrdered = 4, kImplAuto = 5;
+constexpr int kPrecSet = 8;  // precision = kPrecSet | bits
+constexpr int kFormCombined = 1, kFormSplit = 2,
+              kFormBySize = 3;  // resolved only: split from kTwoKernelMinLaunch
+constexpr int kFftFusionOff = 1, kFftFusionOn = 2;
+constexpr unsigned kAutoThreshold = 16384;
+struct Options {
+  int gridder_impl = 0;    // kImpl*
+  int degridder_impl = 0;  // kImplDefault / kImplValu (by environment only) /
+                           // kImplSequential
+  int precision = 0;       // kPrecSet | bits; resolved and still 0: the
+                           // library's choice for the problem (precision_for)
+  int kernel_form = 0;     // kForm*
+  int fft_fusion = 0;      // kFftFusion*
+  unsigned auto_threshold = 0;  // kImplAuto: ordered above this T x C
+  bool resolved = false;
+};
+Options resolve_options(const Options &request);
+
 // Buffer extents used for host-side validation (element counts).
 struct Extents {
   size_t uvw_rows = 0;      // UVW triplets (= visibility rows)
@@ -120,6 +146,11 @@ struct KernelChoice {
   int grid = 0;  // = nr_subgrids
   bool fft_in_kernel = false;  // Problem::fft_out done by these kernels
   int prec = 0;  // precision options of the MFMA kernels (device.hpp kPrec*)
+  // kImplAuto: the kernels above are the default (MFMA) pass, run on a shadow
+  // metadata in which the subgrids above auto_threshold are empty; the
+  // queue-fed ordered kernel then writes those (launch_auto_gridder)
+  bool auto_ordered = false;
+  unsigned auto_threshold = 0;
   // The launch the device entries make instead, when parts[1] is set: one
   // kernel per subgrid class, each with the register allocation of its own
   // path.  parts[0] (kMirror; absent for odd S): grid =
@@ -154,7 +185,7 @@ hipError_t launch_parts(const KernelChoice &k, int nr_subgrids, void **args13,
 // host thread holds the slot, ptr is a private stream-ordered allocation
 // (never clean) freed after the sequence.
 constexpr int kWorkspaceQueue = 0, kWorkspaceHomeSort = 1,
-              kWorkspaceAdderSeg = 2;
+              kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3;
 // Not copyable: a copy would release the slot twice.
 struct WorkspaceLease {
   void *ptr = nullptr;
@@ -186,10 +217,10 @@ hipError_t release_workspaces(hipStream_t stream, bool all);
 // the batch) its fixed cost -- the queue's allocation and clear and a second
 // launch, ~15 us per direction -- outweighs what the mirror kernel's own
 // register allocation saves (one-GPU shard rehearsal at N = 8: 0.953 with
-// it, 0.969 without).  IDG_KERNEL_FORM=combined / split forces either (A/B
-// and tests; read per call).
+// it, 0.969 without).  Options::kernel_form (IDG_KERNEL_FORM=combined /
+// split) forces either.
 constexpr int kTwoKernelMinLaunch = 8192;
-bool two_kernel_form(int nr_subgrids);
+bool two_kernel_form(int nr_subgrids, const Options &opt = Options());
 
 // Precision options (device.hpp kPrecTail | kPrecFlush | kPrecTailAlt) of
 // the MFMA kernels for a launch: the gridder takes
@@ -198,18 +229,20 @@ bool two_kernel_form(int nr_subgrids);
 // reference's own f32 sum) and, above
 // kTailMinChannels channels, blocked summation (kPrecFlush: C = 256 gridder
 // 8.4e-6 -> 2.0e-6 from exact accumulation); the degridder no tail.
-// IDG_PREC=<0..7> forces the bits for both directions (A/B, tests).
+// Options::precision (IDG_PREC=<0..7>) forces the bits for both directions.
 constexpr int kTailMinChannels = 16;
-int precision_for(Direction dir, const Problem &p);
+int precision_for(Direction dir, const Problem &p,
+                  const Options &opt = Options());
 
 // Defined in the kernel TUs.
-KernelChoice select_gridder(const Problem &p);
-KernelChoice select_degridder(const Problem &p);
+KernelChoice select_gridder(const Problem &p, const Options &opt = Options());
+KernelChoice select_degridder(const Problem &p,
+                              const Options &opt = Options());
 
 // The order-preserving kernels (kernels/sequential_mi355x.hip.cpp): the
 // reference CPU path's rounding sequence, bit for bit; 13-argument ABI, grid
 // = nr_subgrids, block = sequential_block().  Selected per call by
-// IDG_GRIDDER_IMPL=sequential / IDG_DEGRIDDER_IMPL=sequential.
+// Options kImplSequential (IDG_GRIDDER_IMPL / IDG_DEGRIDDER_IMPL=sequential).
 const void *sequential_gridder(int subgrid_size);
 const void *sequential_degridder(int subgrid_size);
 int sequential_block();
@@ -217,9 +250,36 @@ int sequential_block();
 // The ordered gridder (kernels/ordered_mi355x.hip.cpp): the reference's
 // summation order and product forms with the hardware sin / cos of the MFMA
 // kernels -- within the reference's 1e-5 bar at any T x C, not bit-exact;
-// same ABI and launch shape.  Selected per call by IDG_GRIDDER_IMPL=ordered.
+// same ABI and launch shape.  Options kImplOrdered (IDG_GRIDDER_IMPL=ordered).
 const void *ordered_gridder(int subgrid_size);
 int ordered_block();
+
+// The auto gridder (Options::gridder_impl = kImplAuto), three
+// stream-ordered steps with no device-to-host copy and no cross-workgroup
+// wait; kernel boundaries order them.  `ws` is auto_workspace_bytes() of
+// workspace: a count, a queue of subgrid indices and a shadow metadata.
+//   launch_auto_classify: one thread per subgrid; subgrids with nr_timesteps
+//     x nr_channels > threshold (64-bit product) are pushed to the queue and
+//     get nr_timesteps = 0 in the shadow copy, the others are copied as is.
+//   (the caller runs the default gridder on auto_shadow(ws))
+//   launch_ordered_queue: the ordered kernel over the queue, true metadata;
+//     `slices` workgroups per queued subgrid, each taking a contiguous range
+//     of whole pixels (a pixel's (t, c) sum is never split, so the bits are
+//     the ordered kernel's).  Grid = nr_subgrids x slices: the host does not
+//     know the count; workgroups past it return at once.
+// kAutoSlices: the slicing the launch layer uses (IDG_AUTO_SLICES, a
+// measurement knob, overrides it).
+size_t auto_workspace_bytes(int nr_subgrids);
+const void *auto_shadow(void *ws, int nr_subgrids);
+hipError_t launch_auto_classify(int nr_subgrids, int nr_channels,
+                                unsigned threshold, const void *d_metadata,
+                                void *ws, hipStream_t stream);
+hipError_t launch_ordered_queue(const Problem &p, void **args13, void *ws,
+                                int slices, hipStream_t stream);
+constexpr int kAutoSlices = 2;
+// Host twin of the classification.
+bool auto_selects(long long nr_timesteps, long long nr_channels,
+                  unsigned threshold);
 
 // Returns an empty string if every subgrid's time range, stations and A-term
 // slot lie inside the buffers, else a description of the first violation.
@@ -233,7 +293,8 @@ hipError_t launch(Direction dir, const Problem &p, const void *d_uvw,
                   const float *d_wavenumbers, void *d_visibilities,
                   const float *d_spheroidal, const void *d_aterms,
                   const void *d_metadata, void *d_subgrids,
-                  hipStream_t stream, const KernelChoice *force = nullptr);
+                  hipStream_t stream, const KernelChoice *force = nullptr,
+                  const Options &opt = Options());
 
 // Synchronous host-buffer pipeline: validate, allocate, H2D, launch, D2H,
 // free.  Returns hipSuccess or the first error; *msg explains validation
@@ -243,7 +304,8 @@ hipError_t run_host(Direction dir, const Problem &p, const Extents &e,
                     void *visibilities, const float *spheroidal,
                     const void *aterms, const idg::Metadata *metadata,
                     void *subgrids, std::string *msg,
-                    const KernelChoice *force = nullptr);
+                    const KernelChoice *force = nullptr,
+                    const Options &opt = Options());
 
 // Chunk plan of run_host: subgrid bounds (nchunk + 1 entries) of
 // consecutive chunks whose visibility rows are disjoint and ascending, and

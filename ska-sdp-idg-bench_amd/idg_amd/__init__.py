@@ -5,7 +5,7 @@ the C ABI of libidg_mi355x.so (include/idg_mi355x.h).  Importing this package
 loads the HIP library and raises if it is missing: there is no CPU fallback.
 """
 from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
-                  IdgError, abi_version, adder_launch, as_metadata,
+                  IdgError, Options, abi_version, auto_selected, adder_launch, as_metadata,
                   bytes_gridder, c_run_degridder, c_run_gridder,
                   degrid_from, degridder_launch, device_name, flops_gridder,
                   generate, grid_onto, gridder_fft_launch, gridder_launch,
@@ -15,7 +15,7 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   release_workspaces,
                   splitter_fft_launch, splitter_launch, subgrid_fft_launch,
                   validate_metadata)
-from ._lib import LIB_PATH
+from ._lib import LIB_PATH, OptionsStruct
 from . import shard
 
 __all__ = [
@@ -27,5 +27,6 @@ __all__ = [
     "precision_options", "release_workspaces",
     "p_run_gridder", "splitter_fft_launch", "splitter_launch",
     "subgrid_fft_launch",
-    "validate_metadata", "LIB_PATH", "shard",
+    "validate_metadata", "LIB_PATH", "shard", "Options", "OptionsStruct",
+    "auto_selected",
 ]

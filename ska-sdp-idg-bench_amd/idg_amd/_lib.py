@@ -53,7 +53,28 @@ SIGNATURES = {
     "idg_splitter_launch": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "idg_splitter_fft_launch": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
     "idg_release_workspaces": (_I, [_P, _I]),
+    # the entries above plus a trailing const idg_options_t *
+    "idg_c_run_gridder_opts": (_I, [_I, _I, _I, _F, _F, _I, _I, _P, _Z, _P,
+                                    _P, _P, _P, _Z, _P, _P, _P]),
+    "idg_c_run_degridder_opts": (_I, [_I, _I, _I, _F, _F, _I, _I, _P, _Z, _P,
+                                      _P, _P, _P, _Z, _P, _P, _P]),
+    "idg_gridder_launch_opts": (_I, [_I, _I, _I, _F, _F, _I, _I, _P, _P, _P,
+                                     _P, _P, _P, _P, _P, _P]),
+    "idg_gridder_fft_launch_opts": (_I, [_I, _I, _I, _F, _F, _I, _I, _P, _P,
+                                         _P, _P, _P, _P, _P, _P, _P]),
+    "idg_degridder_launch_opts": (_I, [_I, _I, _I, _F, _F, _I, _I, _P, _P, _P,
+                                       _P, _P, _P, _P, _P, _P]),
+    "idg_kernel_name_opts": (_S, [_I, _I, _I, _P]),
+    "idg_precision_options_opts": (_I, [_I, _I, _I, _P]),
+    "idg_auto_selected": (_I, [_I, _I, _P, _P, _P]),
 }
+
+
+class OptionsStruct(ctypes.Structure):
+    """idg_options_t (include/idg_mi355x.h); 0 in a field = unset."""
+    _fields_ = [(name, ctypes.c_uint32) for name in (
+        "struct_size", "gridder_impl", "degridder_impl", "precision",
+        "kernel_form", "fft_fusion", "auto_threshold")]
 
 
 def _load():

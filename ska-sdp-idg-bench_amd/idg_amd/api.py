@@ -16,7 +16,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import lib
+from ._lib import OptionsStruct, lib
 
 IMAGE_SIZE = 0.01   # app/common/parameters.hpp:4
 W_STEP = 0.0        # app/common/parameters.hpp:5
@@ -39,6 +39,100 @@ class IdgError(RuntimeError):
 def _check(code, what):
     if code != 0:
         raise IdgError(code, what)
+
+
+# ---------------------------------------------------------------------------
+# Per-call launch options (idg_options_t)
+# ---------------------------------------------------------------------------
+IMPLS = {"default": 1, "valu": 2, "sequential": 3, "ordered": 4, "auto": 5}
+KERNEL_FORMS = {"combined": 1, "split": 2}
+PREC_SET = 8
+AUTO_THRESHOLD = 16384
+
+
+def _enum(value, names, what):
+    if value is None:
+        return 0
+    if isinstance(value, str):
+        if value not in names:
+            raise ValueError(f"{what} must be one of {sorted(names)}, "
+                             f"got {value!r}")
+        return names[value]
+    return int(value)   # a raw IDG_* value; the library checks it
+
+
+class Options:
+    """Which kernels one call runs, instead of the IDG_* environment
+    variables.  None in a field = unset: the variable if it is set, else the
+    library's default; an explicit value wins over the variable.
+
+      gridder     "default" | "valu" | "sequential" | "ordered" | "auto"
+      degridder   "default" | "sequential"
+      precision   0..7, the bits of precision_options()
+      kernel_form "combined" | "split"
+      fft_fusion  False | True (the FFT in the S = 32 gridder's epilogue)
+      auto_threshold  "auto" sends a subgrid to the ordered kernel iff its
+                  nr_timesteps x nr_channels exceeds this (library: 16,384)
+    """
+
+    def __init__(self, gridder=None, degridder=None, precision=None,
+                 kernel_form=None, fft_fusion=None, auto_threshold=None):
+        self.gridder = gridder
+        self.degridder = degridder
+        self.precision = precision
+        self.kernel_form = kernel_form
+        self.fft_fusion = fft_fusion
+        self.auto_threshold = auto_threshold
+
+    def __repr__(self):
+        return "Options(" + ", ".join(
+            f"{k}={v!r}" for k, v in vars(self).items() if v is not None) + ")"
+
+    def struct(self):
+        """The idg_options_t of these options."""
+        o = OptionsStruct()
+        o.struct_size = ctypes.sizeof(OptionsStruct)
+        o.gridder_impl = _enum(self.gridder, IMPLS, "gridder")
+        o.degridder_impl = _enum(self.degridder, IMPLS, "degridder")
+        if self.precision is not None:
+            if not 0 <= int(self.precision) <= 7:
+                raise ValueError("precision must be 0..7")
+            o.precision = PREC_SET | int(self.precision)
+        o.kernel_form = _enum(self.kernel_form, KERNEL_FORMS, "kernel_form")
+        if self.fft_fusion is not None:
+            o.fft_fusion = 2 if self.fft_fusion else 1
+        if self.auto_threshold is not None:
+            if not 0 <= int(self.auto_threshold) < 2 ** 32:
+                raise ValueError("auto_threshold must fit 32 bits")
+            o.auto_threshold = int(self.auto_threshold)
+        return o
+
+
+def _opts_ptr(options):
+    """(keep-alive object, pointer) for an Options, a raw OptionsStruct or
+    None (NULL: the entries' behaviour without options)."""
+    if options is None:
+        return None, None
+    o = options.struct() if isinstance(options, Options) else options
+    if not isinstance(o, OptionsStruct):
+        raise TypeError("options must be an idg_amd.Options")
+    return o, ctypes.cast(ctypes.pointer(o), ctypes.c_void_p)
+
+
+def auto_selected(metadata, nr_channels, options=None):
+    """The subgrids a gridder="auto" launch with `options` sends to the
+    ordered kernel (idg_auto_selected, the host twin of the device
+    classification): a uint8 array, 1 = ordered."""
+    md = as_metadata(metadata)
+    sel = np.zeros(md.size, np.uint8)
+    keep, ptr = _opts_ptr(options)
+    n = lib.idg_auto_selected(md.size, nr_channels, ptr,
+                              _np_ptr(md, METADATA_DTYPE, "metadata"),
+                              sel.ctypes.data_as(ctypes.c_void_p))
+    if n < 0:
+        raise IdgError(n, "auto_selected")
+    assert n == int(sel.sum())
+    return sel
 
 
 def _np_ptr(a, dtype, name, writable=False):
@@ -129,12 +223,13 @@ def _extents(nr_channels, uvw, visibilities, aterms, subgrids, subgrid_size,
 def c_run_gridder(nr_subgrids, grid_size, subgrid_size, image_size,
                   w_step_in_lambda, nr_channels, nr_stations, uvw,
                   wavenumbers, visibilities, spheroidal, aterms, metadata,
-                  subgrids):
+                  subgrids, options=None):
     """Grid visibilities onto subgrids (fills `subgrids` in place)."""
+    keep, optr = _opts_ptr(options)
     md = as_metadata(metadata)
     rows, slots = _extents(nr_channels, uvw, visibilities, aterms, subgrids,
                            subgrid_size, nr_subgrids, nr_stations)
-    _check(lib.idg_c_run_gridder(
+    _check(lib.idg_c_run_gridder_opts(
         nr_subgrids, grid_size, subgrid_size, image_size, w_step_in_lambda,
         nr_channels, nr_stations, _np_ptr(uvw, np.float32, "uvw"), rows,
         _np_ptr(wavenumbers, np.float32, "wavenumbers"),
@@ -142,19 +237,21 @@ def c_run_gridder(nr_subgrids, grid_size, subgrid_size, image_size,
         _np_ptr(spheroidal, np.float32, "spheroidal"),
         _np_ptr(aterms, np.float32, "aterms"), slots,
         _np_ptr(md, METADATA_DTYPE, "metadata"),
-        _np_ptr(subgrids, np.float32, "subgrids", True)), "c_run_gridder")
+        _np_ptr(subgrids, np.float32, "subgrids", True), optr),
+        "c_run_gridder")
     return subgrids
 
 
 def c_run_degridder(nr_subgrids, grid_size, subgrid_size, image_size,
                     w_step_in_lambda, nr_channels, nr_stations, uvw,
                     wavenumbers, visibilities, spheroidal, aterms, metadata,
-                    subgrids):
+                    subgrids, options=None):
     """Degrid subgrids into visibilities (fills `visibilities` in place)."""
+    keep, optr = _opts_ptr(options)
     md = as_metadata(metadata)
     rows, slots = _extents(nr_channels, uvw, visibilities, aterms, subgrids,
                            subgrid_size, nr_subgrids, nr_stations)
-    _check(lib.idg_c_run_degridder(
+    _check(lib.idg_c_run_degridder_opts(
         nr_subgrids, grid_size, subgrid_size, image_size, w_step_in_lambda,
         nr_channels, nr_stations, _np_ptr(uvw, np.float32, "uvw"), rows,
         _np_ptr(wavenumbers, np.float32, "wavenumbers"),
@@ -162,7 +259,7 @@ def c_run_degridder(nr_subgrids, grid_size, subgrid_size, image_size,
         _np_ptr(spheroidal, np.float32, "spheroidal"),
         _np_ptr(aterms, np.float32, "aterms"), slots,
         _np_ptr(md, METADATA_DTYPE, "metadata"),
-        _np_ptr(subgrids, np.float32, "subgrids")), "c_run_degridder")
+        _np_ptr(subgrids, np.float32, "subgrids"), optr), "c_run_degridder")
     return visibilities
 
 
@@ -253,7 +350,7 @@ def _dev_extents(nr_subgrids, subgrid_size, nr_channels, nr_stations, uvw,
 def gridder_launch(nr_subgrids, grid_size, subgrid_size, image_size,
                    w_step_in_lambda, nr_channels, nr_stations, uvw,
                    wavenumbers, visibilities, spheroidal, aterms, metadata,
-                   subgrids, stream=None, validate=False):
+                   subgrids, stream=None, validate=False, options=None):
     """Enqueue the gridder on device-resident tensors (metadata as int32
     [NS, 9] tensor or uint8 view of METADATA_DTYPE); returns immediately.
     Tensor extents are checked on the host; validate=True also checks the
@@ -263,21 +360,22 @@ def gridder_launch(nr_subgrids, grid_size, subgrid_size, image_size,
     _dev_extents(nr_subgrids, subgrid_size, nr_channels, nr_stations, uvw,
                  wavenumbers, visibilities, spheroidal, aterms, metadata,
                  subgrids, validate)
-    _check(lib.idg_gridder_launch(
+    keep, optr = _opts_ptr(options)
+    _check(lib.idg_gridder_launch_opts(
         nr_subgrids, grid_size, subgrid_size, image_size, w_step_in_lambda,
         nr_channels, nr_stations, _dev_ptr(uvw, "uvw", f32),
         _dev_ptr(wavenumbers, "wavenumbers", f32),
         _dev_ptr(visibilities, "visibilities", f32),
         _dev_ptr(spheroidal, "spheroidal", f32),
         _dev_ptr(aterms, "aterms", f32), _dev_ptr(metadata, "metadata"),
-        _dev_ptr(subgrids, "subgrids", f32), _stream_handle(stream)),
+        _dev_ptr(subgrids, "subgrids", f32), _stream_handle(stream), optr),
         "gridder_launch")
 
 
 def gridder_fft_launch(nr_subgrids, grid_size, subgrid_size, image_size,
                        w_step_in_lambda, nr_channels, nr_stations, uvw,
                        wavenumbers, visibilities, spheroidal, aterms, metadata,
-                       subgrids, stream=None, validate=False):
+                       subgrids, stream=None, validate=False, options=None):
     """gridder_launch followed by subgrid_fft_launch(+1, 1.0): the adder's
     input (uv-domain) subgrids; the FFT runs in the gridder's epilogue for
     S = 32, bit for bit the two launches' result."""
@@ -286,21 +384,22 @@ def gridder_fft_launch(nr_subgrids, grid_size, subgrid_size, image_size,
     _dev_extents(nr_subgrids, subgrid_size, nr_channels, nr_stations, uvw,
                  wavenumbers, visibilities, spheroidal, aterms, metadata,
                  subgrids, validate)
-    _check(lib.idg_gridder_fft_launch(
+    keep, optr = _opts_ptr(options)
+    _check(lib.idg_gridder_fft_launch_opts(
         nr_subgrids, grid_size, subgrid_size, image_size, w_step_in_lambda,
         nr_channels, nr_stations, _dev_ptr(uvw, "uvw", f32),
         _dev_ptr(wavenumbers, "wavenumbers", f32),
         _dev_ptr(visibilities, "visibilities", f32),
         _dev_ptr(spheroidal, "spheroidal", f32),
         _dev_ptr(aterms, "aterms", f32), _dev_ptr(metadata, "metadata"),
-        _dev_ptr(subgrids, "subgrids", f32), _stream_handle(stream)),
+        _dev_ptr(subgrids, "subgrids", f32), _stream_handle(stream), optr),
         "gridder_fft_launch")
 
 
 def degridder_launch(nr_subgrids, grid_size, subgrid_size, image_size,
                      w_step_in_lambda, nr_channels, nr_stations, uvw,
                      wavenumbers, visibilities, spheroidal, aterms, metadata,
-                     subgrids, stream=None, validate=False):
+                     subgrids, stream=None, validate=False, options=None):
     """Enqueue the degridder on device-resident tensors; returns immediately.
     Extent checks and `validate` as for gridder_launch."""
     import torch
@@ -308,14 +407,15 @@ def degridder_launch(nr_subgrids, grid_size, subgrid_size, image_size,
     _dev_extents(nr_subgrids, subgrid_size, nr_channels, nr_stations, uvw,
                  wavenumbers, visibilities, spheroidal, aterms, metadata,
                  subgrids, validate)
-    _check(lib.idg_degridder_launch(
+    keep, optr = _opts_ptr(options)
+    _check(lib.idg_degridder_launch_opts(
         nr_subgrids, grid_size, subgrid_size, image_size, w_step_in_lambda,
         nr_channels, nr_stations, _dev_ptr(uvw, "uvw", f32),
         _dev_ptr(wavenumbers, "wavenumbers", f32),
         _dev_ptr(visibilities, "visibilities", f32),
         _dev_ptr(spheroidal, "spheroidal", f32),
         _dev_ptr(aterms, "aterms", f32), _dev_ptr(metadata, "metadata"),
-        _dev_ptr(subgrids, "subgrids", f32), _stream_handle(stream)),
+        _dev_ptr(subgrids, "subgrids", f32), _stream_handle(stream), optr),
         "degridder_launch")
 
 
@@ -393,7 +493,7 @@ def splitter_fft_launch(grid_size, metadata, grid, subgrids, nr_w_layers=1,
 def grid_onto(nr_subgrids, grid_size, subgrid_size, image_size,
               w_step_in_lambda, nr_channels, nr_stations, uvw, wavenumbers,
               visibilities, spheroidal, aterms, metadata, grid,
-              nr_w_layers=1, subgrids=None, stream=None):
+              nr_w_layers=1, subgrids=None, stream=None, options=None):
     """Visibilities -> uv grid: gridder and subgrid FFT (+1), fused for
     S = 32 (gridder_fft_launch), then the adder into `grid` (accumulates).
     Returns the (uv-domain) subgrid scratch."""
@@ -404,7 +504,7 @@ def grid_onto(nr_subgrids, grid_size, subgrid_size, image_size,
     gridder_fft_launch(nr_subgrids, grid_size, subgrid_size, image_size,
                        w_step_in_lambda, nr_channels, nr_stations, uvw,
                        wavenumbers, visibilities, spheroidal, aterms,
-                       metadata, subgrids, stream)
+                       metadata, subgrids, stream, options=options)
     adder_launch(grid_size, metadata, subgrids, grid, nr_w_layers, stream)
     return subgrids
 
@@ -412,7 +512,7 @@ def grid_onto(nr_subgrids, grid_size, subgrid_size, image_size,
 def degrid_from(nr_subgrids, grid_size, subgrid_size, image_size,
                 w_step_in_lambda, nr_channels, nr_stations, uvw, wavenumbers,
                 visibilities, spheroidal, aterms, metadata, grid,
-                nr_w_layers=1, subgrids=None, stream=None):
+                nr_w_layers=1, subgrids=None, stream=None, options=None):
     """uv grid -> visibilities: splitter and subgrid FFT (-1, 1/S^2), fused
     for S = 32 / 64 (splitter_fft_launch), then the degridder (overwrites
     the visibility rows of every subgrid)."""
@@ -425,7 +525,7 @@ def degrid_from(nr_subgrids, grid_size, subgrid_size, image_size,
     degridder_launch(nr_subgrids, grid_size, subgrid_size, image_size,
                      w_step_in_lambda, nr_channels, nr_stations, uvw,
                      wavenumbers, visibilities, spheroidal, aterms, metadata,
-                     subgrids, stream)
+                     subgrids, stream, options=options)
     return subgrids
 
 
@@ -455,9 +555,13 @@ def device_name():
     return buf.value.decode()
 
 
-def kernel_name(direction, subgrid_size, nr_channels):
+def kernel_name(direction, subgrid_size, nr_channels, options=None):
     d = {"gridder": 0, "degridder": 1}.get(direction, direction)
-    return lib.idg_kernel_name(d, subgrid_size, nr_channels).decode()
+    keep, optr = _opts_ptr(options)
+    name = lib.idg_kernel_name_opts(d, subgrid_size, nr_channels, optr)
+    if name is None:
+        raise IdgError(-1, "kernel_name")
+    return name.decode()
 
 
 PRECISION_BITS = {1: "reduction tail on every phasor",
@@ -465,11 +569,15 @@ PRECISION_BITS = {1: "reduction tail on every phasor",
                   4: "reduction tail on one channel per quad"}
 
 
-def precision_options(direction, subgrid_size, nr_channels):
+def precision_options(direction, subgrid_size, nr_channels, options=None):
     """The selected kernels' precision options (include/idg_mi355x.h
     idg_precision_options): (bits, description)."""
     d = {"gridder": 0, "degridder": 1}.get(direction, direction)
-    bits = int(lib.idg_precision_options(d, subgrid_size, nr_channels))
+    keep, optr = _opts_ptr(options)
+    bits = int(lib.idg_precision_options_opts(d, subgrid_size, nr_channels,
+                                              optr))
+    if bits < 0:
+        raise IdgError(bits, "precision_options")
     desc = [v for k, v in PRECISION_BITS.items() if bits & k]
     return bits, "; ".join(desc) if desc else "none"
 
