@@ -398,6 +398,64 @@ int idg_auto_selected(int nr_subgrids, int nr_channels,
                       const idg_options_t *options,
                       const idg_metadata_t *metadata, uint8_t *selected);
 
+/* ---- plan: uvw tracks -> subgrid metadata --------------------
+ * The step between "I have uvw" and the entries above.  No reference
+ * counterpart: the reference's initialize_metadata (app/common/init.cpp)
+ * draws subgrid coordinates at random.  Each baseline's nr_timesteps rows
+ * (row bl * nr_timesteps + t of uvw, metres) are walked in time order and cut
+ * greedily into subgrids: a timestep joins the open subgrid while that has
+ * fewer than max_nr_timesteps_per_subgrid timesteps, the A-term slot
+ * (t / nr_timesteps_per_aterm) and the w layer stay the same, and a subgrid
+ * centred on the uv cells of all its timesteps at the first and the last
+ * channel still has kernel_size cells to spare and lies wholly inside the
+ * grid.  Timesteps with a non-finite coordinate, or whose own cells fit no
+ * subgrid, are dropped (in no subgrid) and counted.  Records are written
+ * baseline-major, in time order, with baseline_offset = 0 and time_offset =
+ * the first row; the w layer (coord_z) is floor(w * mean wavenumber / (2 pi
+ * w_step_in_lambda)) clamped into [0, nr_w_layers - 1], 0 when
+ * w_step_in_lambda is 0.  All arithmetic is float32 and the two entries
+ * produce the same bytes.
+ *
+ * struct_size = sizeof(idg_plan_params_t), with the rules of idg_options_t:
+ * fields beyond a smaller struct_size are zero, bytes past the fields known
+ * here must be zero.  IDG_E_INVALID_ARGUMENT: that, sizes < 1,
+ * kernel_size < 0 or >= subgrid_size, subgrid_size > grid_size,
+ * max_nr_timesteps_per_subgrid < 1, nr_timesteps_per_aterm < 0,
+ * nr_w_layers < 1 or > 2^24, capacity < 0, nr_baselines * nr_timesteps >=
+ * 2^31. */
+typedef struct idg_plan_params_t {
+  uint32_t struct_size; /* sizeof(idg_plan_params_t)                        */
+  int32_t grid_size;
+  int32_t subgrid_size;
+  float image_size;
+  float w_step_in_lambda;
+  int32_t nr_w_layers;
+  int32_t kernel_size; /* uv cells kept free at the subgrid's edge          */
+  int32_t max_nr_timesteps_per_subgrid;
+  int32_t nr_timesteps_per_aterm; /* 0 = one A-term slot                    */
+} idg_plan_params_t;
+
+/* Host pointers, no device needed.  baselines: [nr_baselines][2] station
+ * indices; wavenumbers: monotone, only the first and the last are read.
+ * Writes the first min(needed, capacity) records (metadata may be NULL with
+ * capacity 0), counts[0] = subgrids needed, counts[1] = dropped timesteps.
+ * nthreads > 1 splits the baselines over threads (same bytes). */
+int idg_plan(const idg_plan_params_t *params, int nr_baselines,
+             int nr_timesteps, const uint32_t *baselines, const idg_uvw_t *uvw,
+             int nr_channels, const float *wavenumbers,
+             idg_metadata_t *metadata, int capacity, int32_t counts[2],
+             int nthreads);
+
+/* The same on device pointers (baselines, uvw, wavenumbers, metadata and
+ * counts all in device memory), asynchronous on `stream`; nothing is read
+ * back: the caller reads counts[0] to size the gridder launch.  Its scratch
+ * comes from the workspace cache (idg_release_workspaces). */
+int idg_plan_launch(const idg_plan_params_t *params, int nr_baselines,
+                    int nr_timesteps, const uint32_t *baselines,
+                    const idg_uvw_t *uvw, int nr_channels,
+                    const float *wavenumbers, idg_metadata_t *metadata,
+                    int capacity, int32_t counts[2], void *stream);
+
 #ifdef __cplusplus
 }
 #endif

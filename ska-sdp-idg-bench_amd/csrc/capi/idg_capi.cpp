@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "common/plan.hpp"
 #include "hip/util.hpp"
 #include "lib-hip.hpp"
 
@@ -115,6 +116,62 @@ static_assert(IDG_IMPL_DEFAULT == idg_mi355x::kImplDefault &&
                   IDG_FFT_FUSION_ON == idg_mi355x::kFftFusionOn &&
                   IDG_AUTO_THRESHOLD_DEFAULT == idg_mi355x::kAutoThreshold,
               "idg_options_t values are idg_mi355x::Options values");
+
+// idg_plan_params_t (struct_size rules of idg_options_t) and the sizes of a
+// plan call -> plan::Geometry without its scales, image_size and
+// 1 / w_step_in_lambda (computed here, once, for the host and the device).
+int parse_plan(const idg_plan_params_t *params, int nr_baselines,
+               int nr_timesteps, int nr_channels, int capacity,
+               idg_mi355x::plan::Geometry *g, float *image_size,
+               float *inv_w_step) {
+  if (params == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_plan_params_t: null");
+  const uint32_t size = params->struct_size;
+  if (size < sizeof(uint32_t) || size % 4 != 0 || size > (1u << 16))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_plan_params_t: struct_size " + std::to_string(size) +
+                    " (set it to sizeof(idg_plan_params_t))");
+  idg_plan_params_t v;
+  std::memset(&v, 0, sizeof v);
+  std::memcpy(&v, params, std::min<size_t>(size, sizeof v));
+  const unsigned char *raw = reinterpret_cast<const unsigned char *>(params);
+  for (size_t i = sizeof v; i < size; ++i)
+    if (raw[i] != 0)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "idg_plan_params_t: struct_size " + std::to_string(size) +
+                      " with a field set that this library (struct_size " +
+                      std::to_string(sizeof v) + ") does not know");
+  if (nr_baselines < 1 || nr_timesteps < 1 || nr_channels < 1 || capacity < 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "plan: nr_baselines, nr_timesteps, nr_channels >= 1 and "
+                "capacity >= 0 required");
+  if (static_cast<long long>(nr_baselines) * nr_timesteps >= (1ll << 31))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "plan: nr_baselines * nr_timesteps must be below 2^31");
+  if (v.subgrid_size < 1 || v.grid_size < v.subgrid_size)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "plan: 1 <= subgrid_size <= grid_size required");
+  if (v.kernel_size < 0 || v.kernel_size >= v.subgrid_size)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "plan: 0 <= kernel_size < subgrid_size required");
+  if (v.max_nr_timesteps_per_subgrid < 1 || v.nr_timesteps_per_aterm < 0 ||
+      v.nr_w_layers < 1 || v.nr_w_layers > (1 << 24))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "plan: max_nr_timesteps_per_subgrid >= 1, "
+                "nr_timesteps_per_aterm >= 0, 1 <= nr_w_layers <= 2^24 "
+                "(a layer index is clamped as a float) required");
+  g->grid_size = v.grid_size;
+  g->subgrid_size = v.subgrid_size;
+  g->kernel_size = v.kernel_size;
+  g->max_timesteps = v.max_nr_timesteps_per_subgrid;
+  g->aterm_steps = v.nr_timesteps_per_aterm;
+  g->nr_w_layers = v.nr_w_layers;
+  g->use_w = v.w_step_in_lambda != 0.0f ? 1 : 0;
+  g->s0 = g->s1 = g->ws = 0.0f;
+  *image_size = v.image_size;
+  *inv_w_step = g->use_w ? 1.0f / v.w_step_in_lambda : 0.0f;
+  return IDG_OK;
+}
 
 int check_geometry(const idg_mi355x::Problem &p) {
   if (p.nr_subgrids < 0 || p.subgrid_size <= 0 || p.nr_channels <= 0 ||
@@ -492,6 +549,89 @@ int idg_auto_selected(int nr_subgrids, int nr_channels,
     count += sel ? 1 : 0;
   }
   return count;
+}
+
+int idg_plan(const idg_plan_params_t *params, int nr_baselines,
+             int nr_timesteps, const uint32_t *baselines, const idg_uvw_t *uvw,
+             int nr_channels, const float *wavenumbers,
+             idg_metadata_t *metadata, int capacity, int32_t counts[2],
+             int nthreads) {
+  idg_mi355x::plan::Geometry g;
+  float image_size = 0.0f, inv_w_step = 0.0f;
+  if (int rc = parse_plan(params, nr_baselines, nr_timesteps, nr_channels,
+                          capacity, &g, &image_size, &inv_w_step))
+    return rc;
+  if (!baselines || !uvw || !wavenumbers || !counts ||
+      (capacity > 0 && !metadata))
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_plan: null buffer");
+  idg_mi355x::plan::set_scales(&g, image_size, wavenumbers[0],
+                               wavenumbers[nr_channels - 1], inv_w_step);
+  const int B = nr_baselines, T = nr_timesteps;
+  const float *rows = reinterpret_cast<const float *>(uvw);
+  int32_t *out = reinterpret_cast<int32_t *>(metadata);
+  // count, prefix, fill: each pass splits the baselines over the threads
+  std::vector<int> count(B), dropped(B);
+  std::vector<long long> offset(B + 1, 0);
+  const auto pass = [&](bool fill) {
+    const int nt = std::max(1, std::min(nthreads, B));
+    const auto range = [&](int b0, int b1) {
+      for (int bl = b0; bl < b1; ++bl) {
+        const int row0 = bl * T;
+        int n = 0;
+        const long long first = offset[bl];
+        const int d = idg_mi355x::plan::walk_baseline(
+            g, rows + static_cast<size_t>(row0) * 3, row0, T,
+            baselines[2 * bl], baselines[2 * bl + 1],
+            [&](const int32_t words[9]) {
+              if (fill && first + n < capacity)
+                std::memcpy(out + (first + n) * 9, words, 9 * sizeof(int32_t));
+              ++n;
+            });
+        if (!fill) {
+          count[bl] = n;
+          dropped[bl] = d;
+        }
+      }
+    };
+    if (nt == 1) return range(0, B);
+    std::vector<std::thread> pool;
+    for (int w = 0; w < nt; ++w) {
+      const int b0 = static_cast<int>(static_cast<long long>(B) * w / nt);
+      const int b1 = static_cast<int>(static_cast<long long>(B) * (w + 1) / nt);
+      if (b1 > b0) pool.emplace_back(range, b0, b1);
+    }
+    for (auto &th : pool) th.join();
+  };
+  pass(false);
+  long long lost = 0;
+  for (int bl = 0; bl < B; ++bl) {
+    offset[bl + 1] = offset[bl] + count[bl];
+    lost += dropped[bl];
+  }
+  counts[0] = static_cast<int32_t>(offset[B]);
+  counts[1] = static_cast<int32_t>(lost);
+  if (capacity > 0 && offset[B] > 0) pass(true);
+  return IDG_OK;
+}
+
+int idg_plan_launch(const idg_plan_params_t *params, int nr_baselines,
+                    int nr_timesteps, const uint32_t *baselines,
+                    const idg_uvw_t *uvw, int nr_channels,
+                    const float *wavenumbers, idg_metadata_t *metadata,
+                    int capacity, int32_t counts[2], void *stream) {
+  idg_mi355x::plan::Geometry g;
+  float image_size = 0.0f, inv_w_step = 0.0f;
+  if (int rc = parse_plan(params, nr_baselines, nr_timesteps, nr_channels,
+                          capacity, &g, &image_size, &inv_w_step))
+    return rc;
+  if (!baselines || !uvw || !wavenumbers || !counts ||
+      (capacity > 0 && !metadata))
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_plan_launch: null buffer");
+  return from_hip(idg_mi355x::launch_plan(
+                      g, image_size, inv_w_step, nr_baselines, nr_timesteps,
+                      nr_channels, baselines, uvw, wavenumbers, metadata,
+                      capacity, counts, static_cast<hipStream_t>(stream)),
+                  "idg_plan_launch");
 }
 
 double idg_p_run_gridder(void) {

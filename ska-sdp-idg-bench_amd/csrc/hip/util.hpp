@@ -185,7 +185,7 @@ hipError_t launch_parts(const KernelChoice &k, int nr_subgrids, void **args13,
 // host thread holds the slot, ptr is a private stream-ordered allocation
 // (never clean) freed after the sequence.
 constexpr int kWorkspaceQueue = 0, kWorkspaceHomeSort = 1,
-              kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3;
+              kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3, kWorkspacePlan = 4;
 // Not copyable: a copy would release the slot twice.
 struct WorkspaceLease {
   void *ptr = nullptr;
@@ -280,6 +280,25 @@ constexpr int kAutoSlices = 2;
 // Host twin of the classification.
 bool auto_selects(long long nr_timesteps, long long nr_channels,
                   unsigned threshold);
+
+// The plan step on the device (kernels/plan_mi355x.hip.cpp):
+// uvw rows of nr_baselines x nr_timesteps -> metadata records, bit for bit
+// the host walk of common/plan.hpp.  Three stream-ordered launches (count per
+// baseline, scan, fill) on a kWorkspacePlan lease of plan_workspace_bytes();
+// nothing is read back.  `geometry` carries the integer parameters (its
+// scales are set on the device from d_wavenumbers); d_counts receives
+// {subgrids needed, dropped timesteps}; records past `capacity` are not
+// written.
+namespace plan {
+struct Geometry;
+}
+size_t plan_workspace_bytes(int nr_baselines);
+hipError_t launch_plan(const plan::Geometry &geometry, float image_size,
+                       float inv_w_step, int nr_baselines, int nr_timesteps,
+                       int nr_channels, const void *d_baselines,
+                       const void *d_uvw, const float *d_wavenumbers,
+                       void *d_metadata, int capacity, void *d_counts,
+                       hipStream_t stream);
 
 // Returns an empty string if every subgrid's time range, stations and A-term
 // slot lie inside the buffers, else a description of the first violation.

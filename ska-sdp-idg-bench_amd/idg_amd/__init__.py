@@ -11,11 +11,12 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   generate, grid_onto, gridder_fft_launch, gridder_launch,
                   host_chunk_plan,
                   kernel_name,
-                  nr_subgrids_for, precision_options, p_run_degridder, p_run_gridder,
+                  nr_subgrids_for, plan, plan_launch, precision_options,
+                  p_run_degridder, p_run_gridder,
                   release_workspaces,
                   splitter_fft_launch, splitter_launch, subgrid_fft_launch,
                   validate_metadata)
-from ._lib import LIB_PATH, OptionsStruct
+from ._lib import LIB_PATH, OptionsStruct, PlanParamsStruct
 from . import shard
 
 __all__ = [
@@ -28,5 +29,5 @@ __all__ = [
     "p_run_gridder", "splitter_fft_launch", "splitter_launch",
     "subgrid_fft_launch",
     "validate_metadata", "LIB_PATH", "shard", "Options", "OptionsStruct",
-    "auto_selected",
+    "auto_selected", "plan", "plan_launch", "PlanParamsStruct",
 ]

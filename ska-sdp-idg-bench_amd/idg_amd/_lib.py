@@ -67,6 +67,8 @@ SIGNATURES = {
     "idg_kernel_name_opts": (_S, [_I, _I, _I, _P]),
     "idg_precision_options_opts": (_I, [_I, _I, _I, _P]),
     "idg_auto_selected": (_I, [_I, _I, _P, _P, _P]),
+    "idg_plan": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I]),
+    "idg_plan_launch": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
 }
 
 
@@ -75,6 +77,19 @@ class OptionsStruct(ctypes.Structure):
     _fields_ = [(name, ctypes.c_uint32) for name in (
         "struct_size", "gridder_impl", "degridder_impl", "precision",
         "kernel_form", "fft_fusion", "auto_threshold")]
+
+
+class PlanParamsStruct(ctypes.Structure):
+    """idg_plan_params_t (include/idg_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32),
+                ("grid_size", ctypes.c_int32),
+                ("subgrid_size", ctypes.c_int32),
+                ("image_size", ctypes.c_float),
+                ("w_step_in_lambda", ctypes.c_float),
+                ("nr_w_layers", ctypes.c_int32),
+                ("kernel_size", ctypes.c_int32),
+                ("max_nr_timesteps_per_subgrid", ctypes.c_int32),
+                ("nr_timesteps_per_aterm", ctypes.c_int32)]
 
 
 def _load():

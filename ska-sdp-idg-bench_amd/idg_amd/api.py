@@ -16,7 +16,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import OptionsStruct, lib
+from ._lib import OptionsStruct, PlanParamsStruct, lib
 
 IMAGE_SIZE = 0.01   # app/common/parameters.hpp:4
 W_STEP = 0.0        # app/common/parameters.hpp:5
@@ -527,6 +527,117 @@ def degrid_from(nr_subgrids, grid_size, subgrid_size, image_size,
                      wavenumbers, visibilities, spheroidal, aterms, metadata,
                      subgrids, stream, options=options)
     return subgrids
+
+
+# ---------------------------------------------------------------------------
+# Plan: uvw tracks -> subgrid metadata (idg_plan / idg_plan_launch; not in
+# the reference, whose generator draws the coordinates at random)
+# ---------------------------------------------------------------------------
+def _plan_params(grid_size, subgrid_size, image_size, w_step_in_lambda,
+                 kernel_size, max_nr_timesteps_per_subgrid,
+                 nr_timesteps_per_aterm, nr_w_layers):
+    p = PlanParamsStruct()
+    p.struct_size = ctypes.sizeof(PlanParamsStruct)
+    p.grid_size = grid_size
+    p.subgrid_size = subgrid_size
+    p.image_size = image_size
+    p.w_step_in_lambda = w_step_in_lambda
+    p.nr_w_layers = nr_w_layers
+    p.kernel_size = kernel_size
+    p.max_nr_timesteps_per_subgrid = max_nr_timesteps_per_subgrid
+    p.nr_timesteps_per_aterm = nr_timesteps_per_aterm
+    return p
+
+
+def _plan_shape(uvw_shape, baselines_shape):
+    if len(uvw_shape) != 3 or uvw_shape[2] != 3:
+        raise ValueError("uvw must be [nr_baselines][nr_timesteps][3]")
+    if tuple(baselines_shape) != (uvw_shape[0], 2):
+        raise ValueError(f"baselines must be [{uvw_shape[0]}][2] station "
+                         "indices")
+    return int(uvw_shape[0]), int(uvw_shape[1])
+
+
+def plan(grid_size, subgrid_size, image_size, w_step_in_lambda, uvw,
+         baselines, wavenumbers, kernel_size,
+         max_nr_timesteps_per_subgrid=128, nr_timesteps_per_aterm=0,
+         nr_w_layers=1, nthreads=8):
+    """Cut uvw tracks into subgrids on the host (idg_plan; no device needed).
+    uvw: float32 [B, T, 3] in metres, row bl * T + t; baselines: int32 or
+    uint32 [B, 2] station indices; wavenumbers: float32 [C], monotone.
+    Returns (metadata, dropped): a METADATA_DTYPE array of exactly the
+    subgrids needed (baseline-major, time order; time_offset is the first
+    uvw row, x / y the corner, z the w layer) and the number of timesteps in
+    no subgrid (non-finite, or outside what a subgrid inside the grid with
+    kernel_size cells to spare can hold)."""
+    B, T = _plan_shape(uvw.shape, baselines.shape)
+    if baselines.dtype == np.int32:
+        baselines = baselines.view(np.uint32)
+    params = _plan_params(grid_size, subgrid_size, image_size,
+                          w_step_in_lambda, kernel_size,
+                          max_nr_timesteps_per_subgrid,
+                          nr_timesteps_per_aterm, nr_w_layers)
+    counts = np.zeros(2, np.int32)
+    args = (ctypes.cast(ctypes.pointer(params), ctypes.c_void_p), B, T,
+            _np_ptr(baselines, np.uint32, "baselines"),
+            _np_ptr(uvw, np.float32, "uvw"), wavenumbers.size,
+            _np_ptr(wavenumbers, np.float32, "wavenumbers"))
+    _check(lib.idg_plan(*args, None, 0, counts.ctypes.data_as(
+        ctypes.c_void_p), nthreads), "plan")
+    md = np.zeros(int(counts[0]), METADATA_DTYPE)
+    if md.size:
+        need = int(counts[0])
+        _check(lib.idg_plan(*args, _np_ptr(md, METADATA_DTYPE, "metadata",
+                                           True), md.size,
+                            counts.ctypes.data_as(ctypes.c_void_p), nthreads),
+               "plan")
+        assert int(counts[0]) == need
+    return md, int(counts[1])
+
+
+def plan_launch(grid_size, subgrid_size, image_size, w_step_in_lambda, uvw,
+                baselines, wavenumbers, kernel_size,
+                max_nr_timesteps_per_subgrid=128, nr_timesteps_per_aterm=0,
+                nr_w_layers=1, metadata=None, capacity=None, stream=None):
+    """plan() on device-resident tensors (idg_plan_launch): enqueued on
+    `stream`, nothing is read back.  uvw: float32 [B, T, 3]; baselines: int32
+    [B, 2]; wavenumbers: float32 [C].  Returns (metadata, counts): an int32
+    [capacity, 9] tensor whose first min(counts[0], capacity) records are
+    bit for bit plan()'s, and an int32 [2] tensor {subgrids needed, dropped
+    timesteps}.  capacity defaults to metadata's records, else to B * T,
+    which always suffices; records past counts[0] are left as they were."""
+    import torch
+    B, T = _plan_shape(tuple(uvw.shape), tuple(baselines.shape))
+    if wavenumbers.dim() != 1 or wavenumbers.numel() < 1:
+        raise ValueError("wavenumbers must be [nr_channels]")
+    if metadata is None:
+        if capacity is None:
+            capacity = B * T
+        metadata = torch.empty((capacity, 9), dtype=torch.int32,
+                               device=uvw.device)
+    else:
+        records = metadata.numel() * metadata.element_size() // 36
+        if metadata.numel() * metadata.element_size() % 36:
+            raise ValueError("metadata must hold whole 36-byte records")
+        if capacity is None:
+            capacity = records
+        if capacity > records:
+            raise ValueError(f"metadata holds {records} records, capacity "
+                             f"is {capacity}")
+    counts = torch.empty(2, dtype=torch.int32, device=uvw.device)
+    params = _plan_params(grid_size, subgrid_size, image_size,
+                          w_step_in_lambda, kernel_size,
+                          max_nr_timesteps_per_subgrid,
+                          nr_timesteps_per_aterm, nr_w_layers)
+    _check(lib.idg_plan_launch(
+        ctypes.cast(ctypes.pointer(params), ctypes.c_void_p), B, T,
+        _dev_ptr(baselines, "baselines", torch.int32),
+        _dev_ptr(uvw, "uvw", torch.float32), wavenumbers.numel(),
+        _dev_ptr(wavenumbers, "wavenumbers", torch.float32),
+        _dev_ptr(metadata, "metadata") if capacity > 0 else None,
+        capacity, _dev_ptr(counts, "counts"), _stream_handle(stream)),
+        "plan_launch")
+    return metadata, counts
 
 
 # ---------------------------------------------------------------------------
