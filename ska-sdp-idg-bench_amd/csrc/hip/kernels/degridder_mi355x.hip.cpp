@@ -878,9 +878,7 @@ KernelChoice select_degridder(const Problem &p, const Options &request) {
   if (opt.degridder_impl == kImplSequential) {  // bit-exact to the reference's CPU output
     k.func = sequential_degridder(p.subgrid_size);
     k.block = sequential_block();
-    k.name = p.subgrid_size == 32   ? "degridder_sequential_mi355x_s32"
-             : p.subgrid_size == 64 ? "degridder_sequential_mi355x_s64"
-                                    : "degridder_sequential_mi355x_generic";
+    k.name = IDG_SIZE_NAME("degridder_sequential_mi355x", p.subgrid_size);
     return k;
   }
   k.block = kBlock;
@@ -923,8 +921,7 @@ KernelChoice select_degridder(const Problem &p, const Options &request) {
                    : (cg8 ? IDG_DEGRIDDER_VALU(0, 8) : IDG_DEGRIDDER_VALU(0, 4));
   }
   if (mfma)
-    k.name = s32 ? "degridder_mi355x_s32"
-                 : (s64 ? "degridder_mi355x_s64" : "degridder_mi355x_generic");
+    k.name = IDG_SIZE_NAME("degridder_mi355x", p.subgrid_size);
   else
     k.name = s32 ? "degridder_mi355x_s32_valu"
                  : (s64 ? "degridder_mi355x_s64_valu"

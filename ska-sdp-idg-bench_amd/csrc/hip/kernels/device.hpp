@@ -257,6 +257,62 @@ __device__ __forceinline__ void load_jones(const float4 *p, idg::cfloat *j) {
   j[3] = {b.z, b.w};
 }
 
+// Pixel geometry as the reference gridder forms it (gridder_reference.cpp:
+// 49-64): l, m via double, n = compute_n, phase_offset = fma(w_o, n,
+// fma(u_o, l, v_o*m)).  W_TERMS = false: the caller guarantees w_offset = 0
+// (mirror subgrids), so phase_offset = fma(0, n, x) = x and n (a divide and a
+// square root) is not formed; n is returned as 0.  The order-preserving
+// kernels take W_TERMS = true on mirror subgrids too: fma(0, n, x) formed as
+// the reference forms it.
+template <bool W_TERMS = true>
+__device__ __forceinline__ void pixel_geometry(int p, int S, float image_size,
+                                               const SubgridSetup &g,
+                                               float &l, float &m, float &n,
+                                               float &poff) {
+  const int y = p / S, x = p - (p / S) * S;
+  l = idg::compute_l(x, S, image_size);
+  m = idg::compute_m(y, S, image_size);
+  // phase_offset = fma(w_o, n, fma(u_o, l, v_o*m))
+  if constexpr (W_TERMS) {
+    n = idg::compute_n(l, m);
+    poff = fma_(g.w_offset, n, fma_(g.u_offset, l, g.v_offset * m));
+  } else {
+    n = 0.0f;
+    poff = fma_(g.u_offset, l, g.v_offset * m);
+  }
+}
+
+// Epilogue for one pixel: o = sph * A1^H P A2 (4 correlations) ...
+__device__ __forceinline__ void pixel_out(const float (&a)[8], int p, int S,
+                                          const SubgridSetup &g,
+                                          int nr_stations,
+                                          const float *__restrict__ spheroidal,
+                                          const float2 *__restrict__ aterms,
+                                          float2 (&o)[4]) {
+  const int y = p / S, x = p - (p / S) * S;
+  idg::cfloat pix[4], a1[4], a2[4];
+  for (int q = 0; q < 4; ++q) pix[q] = {a[2 * q], a[2 * q + 1]};
+  load_jones(aterm_ptr(aterms, nr_stations, S, g.aterm_index, g.station1, y,
+                       x), a1);
+  load_jones(aterm_ptr(aterms, nr_stations, S, g.aterm_index, g.station2, y,
+                       x), a2);
+  idg::apply_aterm_gridder(pix, a1, a2);
+  const float sph = spheroidal[p];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) o[q] = make_float2(pix[q].re * sph, pix[q].im * sph);
+}
+
+// ... and its correlation-planar store.
+__device__ __forceinline__ void store_pixel(
+    const float (&a)[8], int p, int S, int npix, const SubgridSetup &g,
+    int nr_stations, const float *__restrict__ spheroidal,
+    const float2 *__restrict__ aterms, float2 *__restrict__ out) {
+  float2 o[4];
+  pixel_out(a, p, S, g, nr_stations, spheroidal, aterms, o);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) out[static_cast<size_t>(q) * npix + p] = o[q];
+}
+
 }  // namespace idg_mi355x
 
 // Debug builds only (-DIDG_WG_TIMELINE=1, tools/debug/wg_timeline.py): per

@@ -31,7 +31,10 @@
 //    serve both pixels.  Subgrids with any w != 0 (or odd S) run the same
 //    GEMMs over every pixel with the w-term in the phase;
 //  * IDG_GRIDDER_IMPL=valu (MODE 0) selects the all-VALU kernel: 16 FMAs per
-//    (pixel, t, c) with wave-uniform visibilities in SGPRs (A/B reference).
+//    (pixel, t, c) with wave-uniform visibilities in SGPRs (A/B reference);
+//  * the pixel geometry and the output epilogue (pixel_geometry, pixel_out,
+//    store_pixel) are device.hpp's, shared with the order-preserving
+//    gridders (seq_common.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -166,59 +169,6 @@ __device__ __forceinline__ void timestep_mirror(
   }
 }
 
-// Epilogue for one pixel: o = sph * A1^H P A2 (4 correlations) ...
-__device__ __forceinline__ void pixel_out(const float (&a)[8], int p, int S,
-                                          const SubgridSetup &g,
-                                          int nr_stations,
-                                          const float *__restrict__ spheroidal,
-                                          const float2 *__restrict__ aterms,
-                                          float2 (&o)[4]) {
-  const int y = p / S, x = p - (p / S) * S;
-  idg::cfloat pix[4], a1[4], a2[4];
-  for (int q = 0; q < 4; ++q) pix[q] = {a[2 * q], a[2 * q + 1]};
-  load_jones(aterm_ptr(aterms, nr_stations, S, g.aterm_index, g.station1, y,
-                       x), a1);
-  load_jones(aterm_ptr(aterms, nr_stations, S, g.aterm_index, g.station2, y,
-                       x), a2);
-  idg::apply_aterm_gridder(pix, a1, a2);
-  const float sph = spheroidal[p];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) o[q] = make_float2(pix[q].re * sph, pix[q].im * sph);
-}
-
-// ... and its correlation-planar store.
-__device__ __forceinline__ void store_pixel(
-    const float (&a)[8], int p, int S, int npix, const SubgridSetup &g,
-    int nr_stations, const float *__restrict__ spheroidal,
-    const float2 *__restrict__ aterms, float2 *__restrict__ out) {
-  float2 o[4];
-  pixel_out(a, p, S, g, nr_stations, spheroidal, aterms, o);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) out[static_cast<size_t>(q) * npix + p] = o[q];
-}
-
-// W_TERMS = false: the caller guarantees w_offset = 0 (mirror subgrids), so
-// phase_offset = fma(0, n, x) = x and n (a divide and a square root) is not
-// formed; n is returned as 0.
-template <bool W_TERMS = true>
-__device__ __forceinline__ void pixel_geometry(int p, int S, float image_size,
-                                               const SubgridSetup &g,
-                                               float &l, float &m, float &n,
-                                               float &poff) {
-  const int y = p / S, x = p - (p / S) * S;
-  l = idg::compute_l(x, S, image_size);
-  m = idg::compute_m(y, S, image_size);
-  // phase_offset = fma(w_o, n, fma(u_o, l, v_o*m))
-  if constexpr (W_TERMS) {
-    n = idg::compute_n(l, m);
-    poff = fma_(g.w_offset, n, fma_(g.u_offset, l, g.v_offset * m));
-  } else {
-    n = 0.0f;
-    poff = fma_(g.u_offset, l, g.v_offset * m);
-  }
-}
-
-
 // ---------------------------------------------------------------------------
 // MFMA mirror path (even S, w = 0 on every timestep, w_offset = 0).
 //
@@ -321,6 +271,22 @@ __device__ __forceinline__ void l2_prefetch_dma(const void *src,
       : "memory");
 }
 
+// The wave's maximum |component| over the workgroup's (NW waves) scan of the
+// n4 float4 at v4; 0 where there is nothing to scan.
+template <int NW>
+__device__ __forceinline__ float wave_max_abs(const float4 *v4, int n4,
+                                              int tid) {
+  float vmax = 0.0f;
+  for (int i = tid; i < n4; i += NW * 64) {
+    const float4 q = v4[i];
+    vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)),
+                             fmaxf(fabsf(q.z), fabsf(q.w))));
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    vmax = fmaxf(vmax, __shfl_xor(vmax, off));
+  return vmax;
+}
+
 // FFT: the subgrid leaves as its 2-D FFT (sign +1, scale 1; S = 32 only),
 // what launch_subgrid_fft(+1, 1) would make of the plain output, bit for
 // bit: the pixels go to LDS planes instead of HBM and fft.hpp's transform
@@ -328,14 +294,15 @@ __device__ __forceinline__ void l2_prefetch_dma(const void *src,
 // PREC: kPrecTail adds the k * phase_index part of the reduction's tail to
 // every phasor's revolutions (device.hpp tail_k_rev: one v_pk_add_f32 per
 // two phasors, ~5 % of the MFMA loop); kPrecTailAlt adds 4x that to the
-// first channel of every quad only (the default: the same sum over each
-// quad for a quarter of the adds); kPrecFlush (S = 32) adds the
-// accumulator tiles to an f32 master every kFlushFills fills and restarts
-// them from zero (blocked summation, DESIGN.md §3.1: the MFMA rounds its
-// f32 sum several times per instruction, so 2,048 K-steps into one tile put
-// the C = 256 gridder 8.4e-6 from exact accumulation).  The master lives in
-// the subgrid's own output slot (32 KB at S = 32, one pass), which only the
-// epilogue writes, after the master is read back.
+// first channel of every quad only (the same sum over each quad for a
+// quarter of the adds; not the default: util.cpp precision_for says why);
+// kPrecFlush (S = 32) adds the accumulator tiles to an f32 master every
+// kFlushFills fills and restarts them from zero (blocked summation,
+// the MFMA rounds its f32 sum several times per instruction,
+// so 2,048 K-steps into one tile put the C = 256 gridder 8.4e-6 from exact
+// accumulation).  The master lives in the subgrid's own output slot (32 KB
+// at S = 32, one pass), which only the epilogue writes, after the master is
+// read back.
 template <int S_CT, int PT, int CB, int NW, bool MIRROR, bool FFT = false,
           int PREC = kPrecTail, bool PRESCAN = false,
           int FILL_D = IDG_GRID_FILL_DEPTH>
@@ -407,17 +374,10 @@ __device__ __forceinline__ void grid_mfma(
   float vmax = vmax_pre;
   if (tid < 2) slots[tid] = 0u;
   if constexpr (!PRESCAN) {
-    vmax = 0.0f;
     const float4 *v4 = reinterpret_cast<const float4 *>(
         visibilities + g.time_offset * C * 4);
     const int n4 = min(4 * quads_per_fill, nt) * C * 2;
-    for (int i = tid; i < n4; i += NW * 64) {
-      const float4 q = v4[i];
-      vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)),
-                               fmaxf(fabsf(q.z), fabsf(q.w))));
-    }
-    for (int off = 32; off > 0; off >>= 1)
-      vmax = fmaxf(vmax, __shfl_xor(vmax, off));
+    vmax = wave_max_abs<NW>(v4, n4, tid);
     float *red = reinterpret_cast<float *>(lds + Lds::kRedOff);
     if (lane == 0) red[wave] = vmax;
     __syncthreads();
@@ -1040,14 +1000,7 @@ __device__ __forceinline__ bool prologue_scan(
   const float4 *v4 = reinterpret_cast<const float4 *>(
       visibilities + g.time_offset * C * 4);
   const int n4 = min(4 * quads_per_fill, g.nr_timesteps) * C * 2;
-  float vmax = 0.0f;
-  for (int i = tid; i < n4; i += NW * 64) {
-    const float4 q = v4[i];
-    vmax = fmaxf(vmax, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)),
-                             fmaxf(fabsf(q.z), fabsf(q.w))));
-  }
-  for (int off = 32; off > 0; off >>= 1)
-    vmax = fmaxf(vmax, __shfl_xor(vmax, off));
+  const float vmax = wave_max_abs<NW>(v4, n4, tid);
   if ((tid & 63) == 0) red[tid >> 6] = vmax;
   return w_nonzero;
 }
@@ -1397,17 +1350,13 @@ KernelChoice select_gridder(const Problem &p, const Options &request) {
   if (impl == kImplSequential) {
     k.func = sequential_gridder(p.subgrid_size);
     k.block = sequential_block();
-    k.name = p.subgrid_size == 32   ? "gridder_sequential_mi355x_s32"
-             : p.subgrid_size == 64 ? "gridder_sequential_mi355x_s64"
-                                    : "gridder_sequential_mi355x_generic";
+    k.name = IDG_SIZE_NAME("gridder_sequential_mi355x", p.subgrid_size);
     return k;  // no FFT epilogue: launch() runs launch_subgrid_fft after it
   }
   if (impl == kImplOrdered) {  // one combined launch, k.prec = 0, no epilogue
     k.func = ordered_gridder(p.subgrid_size);
     k.block = ordered_block();
-    k.name = p.subgrid_size == 32   ? "gridder_ordered_mi355x_s32"
-             : p.subgrid_size == 64 ? "gridder_ordered_mi355x_s64"
-                                    : "gridder_ordered_mi355x_generic";
+    k.name = IDG_SIZE_NAME("gridder_ordered_mi355x", p.subgrid_size);
     return k;
   }
   const bool mfma = impl != kImplValu;
@@ -1454,9 +1403,7 @@ KernelChoice select_gridder(const Problem &p, const Options &request) {
   }
   k.func = set.combined;
   if (auto_ordered)
-    k.name = p.subgrid_size == 32   ? "gridder_auto_mi355x_s32"
-             : p.subgrid_size == 64 ? "gridder_auto_mi355x_s64"
-                                    : "gridder_auto_mi355x_generic";
+    k.name = IDG_SIZE_NAME("gridder_auto_mi355x", p.subgrid_size);
   if (mfma && two_kernel_form(p.nr_subgrids, opt)) {
     if (set.mirror)
       k.parts[0] = {set.mirror, k.block, KernelChoice::kMirror,

@@ -27,13 +27,15 @@
 // Selected by Options::gridder_impl = kImplOrdered (IDG_GRIDDER_IMPL=ordered;
 // util.hpp select_gridder); the 13-argument kernel ABI, grid = nr_subgrids,
 // block = 256.  The auto gridder's queue-fed variant is at the end of this
-// file.  Layout of the work as the sequential gridder: a lane owns pixels
-// whole (8 f32 accumulators each), the visibilities and (u, v, w, k) come
-// through LDS kSeqStage (t, c) items at a time, and on mirror subgrids (even
-// S, w = 0 and w_offset = 0) pixel npix-1-p takes the base pixel's phasor
-// conjugated wherever its own phase is the bitwise negation of the base
-// phase -- checked per phasor; where it is not, the mirror's own phasor is
-// evaluated.  No sincosf tables: the LDS holds the staged block only.
+// file.  The work is laid out as in the sequential gridder, by the same code
+// (seq_common.hpp order_grid_pixels; this file supplies HardwarePhasor and
+// the kernels): a lane owns pixels whole (8 f32 accumulators each), the
+// visibilities and (u, v, w, k) come through LDS kSeqStage (t, c) items at a
+// time, and on mirror subgrids (even S, w = 0 and w_offset = 0) pixel
+// npix-1-p takes the base pixel's phasor conjugated wherever its own phase
+// is the bitwise negation of the base phase -- checked per phasor; where it
+// is not, the mirror's own phasor is evaluated.  No sincosf tables: the LDS
+// holds the staged block only.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -46,101 +48,26 @@ namespace idg_mi355x {
 
 namespace {
 
-// The phasor of phase ph (radians): Dekker reduction to revolutions, then
-// v_sin_f32 / v_cos_f32 on |r| <= 0.5.
-__device__ __forceinline__ void ord_phasor(float ph, float *sn, float *cs) {
-  sincos_rev(revolutions(ph), sn, cs);
-}
-
-// NP base pixels of this lane (base[i] < nbase; clamped duplicates are
-// computed and not stored) and, with MIRROR, their mirrors npix-1-base[i].
-template <int NP, bool MIRROR>
-__device__ __forceinline__ void ord_grid_pixels(
-    const int (&base)[NP], int nbase, int S, int npix, float image_size,
-    const SubgridSetup &g, int C, int nr_stations,
-    const idg::UVWCoordinate<float> *__restrict__ uvw,
-    const float *__restrict__ wavenumbers,
-    const float2 *__restrict__ visibilities,
-    const float *__restrict__ spheroidal, const float2 *__restrict__ aterms,
-    float2 *__restrict__ out, float4 *__restrict__ st_vis,
-    float4 *__restrict__ st_uvwk) {
-  constexpr int NQ = MIRROR ? 2 * NP : NP;
-  float l[NQ], m[NQ], n[NQ], po[NQ];
-  f2v acc[NQ][4];
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    const int b = min(base[i % NP], nbase - 1);
-    const int p = i < NP ? b : npix - 1 - b;
-    seq_geometry(p, S, image_size, g, l[i], m[i], n[i], po[i]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f2v{0.0f, 0.0f};
+// The phasor policy of seq_common.hpp's order_grid_pixels: Dekker reduction
+// of the phase (radians) to revolutions, then v_sin_f32 / v_cos_f32 on |r| <=
+// 0.5.  The mirror's phasor is evaluated on every lane, then replaced by the
+// conjugate where its phase is the negation: the same value whichever branch
+// the wave takes.
+struct HardwarePhasor {
+  __device__ __forceinline__ void operator()(float ph, float *sn,
+                                             float *cs) const {
+    sincos_rev(revolutions(ph), sn, cs);
   }
-  // kSeqStage (t, c) items at a time through LDS, in the reference's
-  // t-then-c order, staged by the workgroup between two barriers
-  const long long items = static_cast<long long>(g.nr_timesteps) * C;
-  const float4 *vis4 = reinterpret_cast<const float4 *>(visibilities) +
-                       g.time_offset * C * 2;
-  float pidx[NQ];
-  for (long long i0 = 0; i0 < items; i0 += kSeqStage) {
-    const int ne = static_cast<int>(items - i0 < kSeqStage ? items - i0 : kSeqStage);
-    __syncthreads();  // the previous block's readers are done
-    for (int e = threadIdx.x; e < ne; e += kSeqBlock) {
-      const long long it = i0 + e;
-      const int t = static_cast<int>(it / C), c = static_cast<int>(it % C);
-      st_vis[2 * e] = vis4[it * 2];
-      st_vis[2 * e + 1] = vis4[it * 2 + 1];
-      const idg::UVWCoordinate<float> c3 = uvw[g.time_offset + t];
-      st_uvwk[e] = make_float4(c3.u, c3.v, c3.w, wavenumbers[c]);
-    }
-    __syncthreads();
-    int ch = static_cast<int>(i0 % C);
-    for (int e = 0; e < ne; ++e) {
-      const float4 uvwk = st_uvwk[e];
-      const float4 va = st_vis[2 * e], vb = st_vis[2 * e + 1];
-      if (ch == 0 || e == 0) {  // a new timestep (or block): phase_index
-#pragma unroll
-        for (int i = 0; i < NQ; ++i)
-          pidx[i] = fma_(uvwk.z, n[i], fma_(uvwk.x, l[i], uvwk.y * m[i]));
-      }
-      ch = ch + 1 == C ? 0 : ch + 1;
-      const float k = uvwk.w;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const float ph = fma_(-pidx[i], k, po[i]);
-        float sn, cs;
-        ord_phasor(ph, &sn, &cs);
-        if constexpr (MIRROR) {
-          // the mirror's own phase, formed as the reference forms it; where
-          // it is the exact negation its phasor is the conjugate, and one
-          // set of products serves both pixels
-          const float phm = fma_(-pidx[NP + i], k, po[NP + i]);
-          const bool neg = fbits(phm) == (fbits(ph) ^ 0x80000000u);
-          if (__all(neg)) {
-            mac_ref_pair(acc[i], acc[NP + i], va, vb, cs, sn);
-          } else {
-            float snm, csm;
-            ord_phasor(phm, &snm, &csm);
-            if (neg) {  // the same value whichever branch the wave takes
-              snm = -sn;
-              csm = cs;
-            }
-            mac_ref(acc[i], va, vb, cs, sn);
-            mac_ref(acc[NP + i], va, vb, csm, snm);
-          }
-        } else {
-          mac_ref(acc[i], va, vb, cs, sn);
-        }
-      }
+  __device__ __forceinline__ void mirror(float phm, bool neg, float sn,
+                                         float cs, float *snm,
+                                         float *csm) const {
+    (*this)(phm, snm, csm);
+    if (neg) {
+      *snm = -sn;
+      *csm = cs;
     }
   }
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    if (base[i % NP] >= nbase) continue;
-    const int p = i < NP ? base[i] : npix - 1 - base[i - NP];
-    seq_store_pixel(acc[i], p, S, npix, g, nr_stations, spheroidal, aterms,
-                    out);
-  }
-}
+};
 
 }  // namespace
 
@@ -166,11 +93,7 @@ __global__ void __launch_bounds__(kSeqBlock)
   const SubgridSetup g = setup_subgrid(metadata, s, grid_size, S, image_size,
                                        w_step_in_lambda);
   float2 *out = subgrids + static_cast<size_t>(s) * 4 * npix;
-  bool w_nonzero = false;
-  for (int t = tid; t < g.nr_timesteps; t += kSeqBlock)
-    w_nonzero |= uvw[g.time_offset + t].w != 0.0f;
-  const bool mirror = __syncthreads_or(w_nonzero) == 0 && S % 2 == 0 &&
-                      g.w_offset == 0.0f;
+  const bool mirror = mirror_eligible(g, S, uvw, tid);
   if (mirror) {
     constexpr int NP = 2;
     const int half = npix / 2;
@@ -178,10 +101,10 @@ __global__ void __launch_bounds__(kSeqBlock)
       int base[NP];
 #pragma unroll
       for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
-      ord_grid_pixels<NP, true>(base, half, S, npix, image_size, g,
-                                nr_channels, nr_stations, uvw, wavenumbers,
-                                visibilities, spheroidal, aterms, out, st_vis,
-                                st_uvwk);
+      order_grid_pixels<NP, true>(base, half, S, npix, image_size, g,
+                                  nr_channels, nr_stations, uvw, wavenumbers,
+                                  visibilities, spheroidal, aterms, out,
+                                  st_vis, st_uvwk, HardwarePhasor{});
     }
     return;
   }
@@ -190,23 +113,19 @@ __global__ void __launch_bounds__(kSeqBlock)
     int base[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
-    ord_grid_pixels<NP, false>(base, npix, S, npix, image_size, g,
-                               nr_channels, nr_stations, uvw, wavenumbers,
-                               visibilities, spheroidal, aterms, out, st_vis,
-                               st_uvwk);
+    order_grid_pixels<NP, false>(base, npix, S, npix, image_size, g,
+                                 nr_channels, nr_stations, uvw, wavenumbers,
+                                 visibilities, spheroidal, aterms, out,
+                                 st_vis, st_uvwk, HardwarePhasor{});
   }
 }
 
 // The ordered gridder of subgrid size S (32, 64, or 0 = runtime S).
 const void *ordered_gridder(int S) {
-  switch (S) {
-    case 32: return reinterpret_cast<const void *>(
-        &kernel_gridder_ordered_mi355x<32>);
-    case 64: return reinterpret_cast<const void *>(
-        &kernel_gridder_ordered_mi355x<64>);
-    default: return reinterpret_cast<const void *>(
-        &kernel_gridder_ordered_mi355x<0>);
-  }
+  return kernel_for_size(S, [](auto s) {
+    return reinterpret_cast<const void *>(
+        &kernel_gridder_ordered_mi355x<decltype(s)::value>);
+  });
 }
 
 int ordered_block() { return kSeqBlock; }
@@ -303,11 +222,7 @@ __global__ void __launch_bounds__(kSeqBlock)
   const SubgridSetup g = setup_subgrid(metadata, s, grid_size, S, image_size,
                                        w_step_in_lambda);
   float2 *out = subgrids + static_cast<size_t>(s) * 4 * npix;
-  bool w_nonzero = false;
-  for (int t = tid; t < g.nr_timesteps; t += kSeqBlock)
-    w_nonzero |= uvw[g.time_offset + t].w != 0.0f;
-  const bool mirror = __syncthreads_or(w_nonzero) == 0 && S % 2 == 0 &&
-                      g.w_offset == 0.0f;
+  const bool mirror = mirror_eligible(g, S, uvw, tid);
   const int nbase = mirror ? npix / 2 : npix;
   const int span = (nbase + slices - 1) / slices;
   const int lo = slice * span, hi = min(nbase, lo + span);
@@ -317,9 +232,10 @@ __global__ void __launch_bounds__(kSeqBlock)
       int base[NP];
 #pragma unroll
       for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
-      ord_grid_pixels<NP, true>(base, hi, S, npix, image_size, g, nr_channels,
-                                nr_stations, uvw, wavenumbers, visibilities,
-                                spheroidal, aterms, out, st_vis, st_uvwk);
+      order_grid_pixels<NP, true>(base, hi, S, npix, image_size, g,
+                                  nr_channels, nr_stations, uvw, wavenumbers,
+                                  visibilities, spheroidal, aterms, out,
+                                  st_vis, st_uvwk, HardwarePhasor{});
     }
     return;
   }
@@ -328,9 +244,10 @@ __global__ void __launch_bounds__(kSeqBlock)
     int base[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
-    ord_grid_pixels<NP, false>(base, hi, S, npix, image_size, g, nr_channels,
-                               nr_stations, uvw, wavenumbers, visibilities,
-                               spheroidal, aterms, out, st_vis, st_uvwk);
+    order_grid_pixels<NP, false>(base, hi, S, npix, image_size, g,
+                                 nr_channels, nr_stations, uvw, wavenumbers,
+                                 visibilities, spheroidal, aterms, out,
+                                 st_vis, st_uvwk, HardwarePhasor{});
   }
 }
 
@@ -350,15 +267,13 @@ hipError_t launch_ordered_queue(const Problem &p, void **args13, void *ws,
                                 int slices, hipStream_t stream) {
   // whole pixels per lane: one slice keeps the ordered kernel's 2 (+ their
   // mirrors), finer slicings take 1
-#define IDG_ORDERED_QUEUE(S_)                                              \
-  (slices > 1 ? reinterpret_cast<const void *>(                            \
-                    &kernel_gridder_ordered_queue_mi355x<S_, 1>)           \
-              : reinterpret_cast<const void *>(                            \
-                    &kernel_gridder_ordered_queue_mi355x<S_, 2>))
-  const void *func = p.subgrid_size == 32   ? IDG_ORDERED_QUEUE(32)
-                     : p.subgrid_size == 64 ? IDG_ORDERED_QUEUE(64)
-                                            : IDG_ORDERED_QUEUE(0);
-#undef IDG_ORDERED_QUEUE
+  const void *func = kernel_for_size(p.subgrid_size, [slices](auto s) {
+    constexpr int S_CT = decltype(s)::value;
+    return slices > 1 ? reinterpret_cast<const void *>(
+                            &kernel_gridder_ordered_queue_mi355x<S_CT, 1>)
+                      : reinterpret_cast<const void *>(
+                            &kernel_gridder_ordered_queue_mi355x<S_CT, 2>);
+  });
   void *args[15];
   for (int i = 0; i < 13; ++i) args[i] = args13[i];
   args[13] = &ws;

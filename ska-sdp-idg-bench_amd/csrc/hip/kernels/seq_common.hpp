@@ -1,6 +1,7 @@
 // seq_common.hpp -- what the kernels that keep the reference's summation
-// order share: the reference's complex multiply-accumulate, pixel geometry
-// and output epilogue, restated for gfx950.  Included by
+// order share: the reference's complex multiply-accumulate restated for
+// gfx950, the mirror-eligibility check, and the gridders' pixel-sum body
+// (order_grid_pixels, the phasor a policy).  Included by
 // sequential_mi355x.hip.cpp (glibc sincosf: the reference's bits) and
 // ordered_mi355x.hip.cpp (hardware sin / cos: the reference's order).
 #pragma once
@@ -64,40 +65,134 @@ __device__ __forceinline__ void mac_ref_pair(f2v (&a)[4], f2v (&b)[4],
   }
 }
 
-// Output pixel p: sph * (A1^H P A2) with the reference's forms (common/
-// math.hpp apply_aterm_gridder), correlation-planar store.
+// Output pixel p: device.hpp's epilogue and correlation-planar store on the
+// packed accumulators.
 __device__ __forceinline__ void seq_store_pixel(
     const f2v (&a)[4], int p, int S, int npix, const SubgridSetup &g,
     int nr_stations, const float *__restrict__ spheroidal,
     const float2 *__restrict__ aterms, float2 *__restrict__ out) {
-  const int y = p / S, x = p - y * S;
-  idg::cfloat pix[4], a1[4], a2[4];
+  float r[8];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) pix[q] = {a[q].x, a[q].y};
-  load_jones(aterm_ptr(aterms, nr_stations, S, g.aterm_index, g.station1, y,
-                       x), a1);
-  load_jones(aterm_ptr(aterms, nr_stations, S, g.aterm_index, g.station2, y,
-                       x), a2);
-  idg::apply_aterm_gridder(pix, a1, a2);
-  const float sph = spheroidal[p];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    out[static_cast<size_t>(q) * npix + p] =
-        make_float2(pix[q].re * sph, pix[q].im * sph);
+  for (int q = 0; q < 4; ++q) {
+    r[2 * q] = a[q].x;
+    r[2 * q + 1] = a[q].y;
+  }
+  store_pixel(r, p, S, npix, g, nr_stations, spheroidal, aterms, out);
 }
 
-// Pixel geometry as the reference gridder forms it (gridder_reference.cpp:
-// 49-64): l, m via double, n = compute_n, phase_offset = fma(w_o, n,
-// fma(u_o, l, v_o*m)) -- with n on mirror subgrids too (w_offset = 0 there,
-// but fma(0, n, x) is formed exactly as the reference forms it).
-__device__ __forceinline__ void seq_geometry(int p, int S, float image_size,
-                                             const SubgridSetup &g, float &l,
-                                             float &m, float &n, float &poff) {
-  const int y = p / S, x = p - y * S;
-  l = idg::compute_l(x, S, image_size);
-  m = idg::compute_m(y, S, image_size);
-  n = idg::compute_n(l, m);
-  poff = fma_(g.w_offset, n, fma_(g.u_offset, l, g.v_offset * m));
+// Mirror pairs need an even S and w = 0 on every timestep and in the offset
+// of the subgrid (as the MFMA kernels).  A barrier: every lane of the
+// workgroup calls it.  Not called by the VALU gridder (its block is
+// blockDim.x), the degridder (its check avoids __syncthreads_or's LDS) and
+// the MFMA gridder's prologue_scan (fused with the max scan).
+__device__ __forceinline__ bool mirror_eligible(
+    const SubgridSetup &g, int S,
+    const idg::UVWCoordinate<float> *__restrict__ uvw, int tid) {
+  bool w_nonzero = false;
+  for (int t = tid; t < g.nr_timesteps; t += kSeqBlock)
+    w_nonzero |= uvw[g.time_offset + t].w != 0.0f;
+  return __syncthreads_or(w_nonzero) == 0 && S % 2 == 0 && g.w_offset == 0.0f;
+}
+
+// The pixel sums of the order-preserving gridders: NP base pixels of this
+// lane (base[i] < nbase; clamped duplicates are computed and not stored) and,
+// with MIRROR, their mirrors npix-1-base[i], each summed over t then c as
+// the reference sums it.  The two gridders share this body and differ in the
+// Phasor policy alone:
+//   phasor(ph, &sn, &cs)                          sin / cos of the phase ph;
+//   phasor.mirror(phm, neg, sn, cs, &snm, &csm)   the same for the mirror's
+//     phase phm: the conjugate of (sn, cs) on lanes where neg (phm is the
+//     bitwise negation of ph), the mirror's own phasor elsewhere.
+template <int NP, bool MIRROR, typename Phasor>
+__device__ __forceinline__ void order_grid_pixels(
+    const int (&base)[NP], int nbase, int S, int npix, float image_size,
+    const SubgridSetup &g, int C, int nr_stations,
+    const idg::UVWCoordinate<float> *__restrict__ uvw,
+    const float *__restrict__ wavenumbers,
+    const float2 *__restrict__ visibilities,
+    const float *__restrict__ spheroidal, const float2 *__restrict__ aterms,
+    float2 *__restrict__ out, float4 *__restrict__ st_vis,
+    float4 *__restrict__ st_uvwk, const Phasor &phasor) {
+  constexpr int NQ = MIRROR ? 2 * NP : NP;
+  float l[NQ], m[NQ], n[NQ], po[NQ];
+  f2v acc[NQ][4];
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    const int b = min(base[i % NP], nbase - 1);
+    const int p = i < NP ? b : npix - 1 - b;
+    pixel_geometry<true>(p, S, image_size, g, l[i], m[i], n[i], po[i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f2v{0.0f, 0.0f};
+  }
+  // The visibilities come through LDS, kSeqStage (t, c) items at a time,
+  // in the reference's t-then-c order: the workgroup stages a block (both
+  // correlation quads of each item and its (u, v, w, k)) between two
+  // barriers, and every wave walks it.  Loaded per wave from global memory
+  // instead (wave-uniform scalar loads), each channel waited on its loads
+  // at the top of the loop -- the lgkm counter they share with the LDS
+  // reads of the sincosf windows makes every window wait a wait for them
+  // too (the sequential gridder issued at 0.90 of its instruction stream,
+  // round 6).
+  const long long items = static_cast<long long>(g.nr_timesteps) * C;
+  const float4 *vis4 = reinterpret_cast<const float4 *>(visibilities) +
+                       g.time_offset * C * 2;
+  float pidx[NQ];
+  for (long long i0 = 0; i0 < items; i0 += kSeqStage) {
+    const int ne = static_cast<int>(items - i0 < kSeqStage ? items - i0 : kSeqStage);
+    __syncthreads();  // the previous block's readers are done
+    for (int e = threadIdx.x; e < ne; e += kSeqBlock) {
+      const long long it = i0 + e;
+      const int t = static_cast<int>(it / C), c = static_cast<int>(it % C);
+      st_vis[2 * e] = vis4[it * 2];
+      st_vis[2 * e + 1] = vis4[it * 2 + 1];
+      const idg::UVWCoordinate<float> c3 = uvw[g.time_offset + t];
+      st_uvwk[e] = make_float4(c3.u, c3.v, c3.w, wavenumbers[c]);
+    }
+    __syncthreads();
+    int ch = static_cast<int>(i0 % C);
+    for (int e = 0; e < ne; ++e) {
+      const float4 uvwk = st_uvwk[e];
+      const float4 va = st_vis[2 * e], vb = st_vis[2 * e + 1];
+      if (ch == 0 || e == 0) {  // a new timestep (or block): phase_index
+#pragma unroll
+        for (int i = 0; i < NQ; ++i)
+          pidx[i] = fma_(uvwk.z, n[i], fma_(uvwk.x, l[i], uvwk.y * m[i]));
+      }
+      ch = ch + 1 == C ? 0 : ch + 1;
+      const float k = uvwk.w;
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const float ph = fma_(-pidx[i], k, po[i]);
+        float sn, cs;
+        phasor(ph, &sn, &cs);
+        if constexpr (MIRROR) {
+          // the mirror's own phase, formed as the reference forms it; where
+          // it is the exact negation (every lane of every wave on the
+          // benchmark data) its phasor is the conjugate, and one set of
+          // products serves both pixels
+          const float phm = fma_(-pidx[NP + i], k, po[NP + i]);
+          const bool neg = fbits(phm) == (fbits(ph) ^ 0x80000000u);
+          if (__all(neg)) {
+            mac_ref_pair(acc[i], acc[NP + i], va, vb, cs, sn);
+          } else {
+            float snm, csm;
+            phasor.mirror(phm, neg, sn, cs, &snm, &csm);
+            mac_ref(acc[i], va, vb, cs, sn);
+            mac_ref(acc[NP + i], va, vb, csm, snm);
+          }
+        } else {
+          mac_ref(acc[i], va, vb, cs, sn);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    if (base[i % NP] >= nbase) continue;
+    const int p = i < NP ? base[i] : npix - 1 - base[i - NP];
+    seq_store_pixel(acc[i], p, S, npix, g, nr_stations, spheroidal, aterms,
+                    out);
+  }
 }
 
 }  // namespace

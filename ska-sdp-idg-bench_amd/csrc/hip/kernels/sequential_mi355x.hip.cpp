@@ -38,7 +38,9 @@
 //    the exact negated phase, and glibc's sincosf is exactly odd / even
 //    (tests/test_host.py: every finite float), so one sincosf serves both;
 //    the lane checks the negation bit for bit per phasor and evaluates the
-//    mirror's own sincosf where it does not hold.
+//    mirror's own sincosf where it does not hold.  The pixel sums are
+//    seq_common.hpp's order_grid_pixels, the body the ordered gridder runs
+//    too; this file supplies its phasor (GlibcPhasor) and the kernel.
 //  * degridder: one workgroup per subgrid; the A-termed, tapered pixels and
 //    their (l, m, n, phase_offset) go to LDS in chunks of 1,024 pixels; a
 //    lane owns (t, c) visibilities and sums over the pixels in y, x order,
@@ -57,97 +59,24 @@ namespace idg_mi355x {
 
 namespace {
 
-// NP base pixels of this lane (base[i] < nbase; clamped duplicates are
-// computed and not stored) and, with MIRROR, their mirrors npix-1-base[i].
-template <int NP, bool MIRROR>
-__device__ __forceinline__ void seq_grid_pixels(
-    const int (&base)[NP], int nbase, int S, int npix, float image_size,
-    const SubgridSetup &g, int C, int nr_stations,
-    const idg::UVWCoordinate<float> *__restrict__ uvw,
-    const float *__restrict__ wavenumbers,
-    const float2 *__restrict__ visibilities,
-    const float *__restrict__ spheroidal, const float2 *__restrict__ aterms,
-    float2 *__restrict__ out, const idg::SincosfWindow *__restrict__ win,
-    float4 *__restrict__ st_vis, float4 *__restrict__ st_uvwk) {
-  constexpr int NQ = MIRROR ? 2 * NP : NP;
-  float l[NQ], m[NQ], n[NQ], po[NQ];
-  f2v acc[NQ][4];
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    const int b = min(base[i % NP], nbase - 1);
-    const int p = i < NP ? b : npix - 1 - b;
-    seq_geometry(p, S, image_size, g, l[i], m[i], n[i], po[i]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f2v{0.0f, 0.0f};
+// The phasor policy of seq_common.hpp's order_grid_pixels: glibc's sincosf
+// from the LDS windows.  The mirror starts from the conjugate (glibc's
+// sincosf is exactly odd / even) and evaluates its own sincosf only where
+// its phase is not the negation.
+struct GlibcPhasor {
+  const idg::SincosfWindow *__restrict__ win;
+  __device__ __forceinline__ void operator()(float ph, float *sn,
+                                             float *cs) const {
+    idg::sincosf_glibc_dev(ph, sn, cs, win);
   }
-  // The visibilities come through LDS, kSeqStage (t, c) items at a time,
-  // in the reference's t-then-c order: the workgroup stages a block (both
-  // correlation quads of each item and its (u, v, w, k)) between two
-  // barriers, and every wave walks it.  Loaded per wave from global memory
-  // instead (wave-uniform scalar loads), each channel waited on its loads
-  // at the top of the loop -- the lgkm counter they share with the LDS
-  // reads of the sincosf windows makes every window wait a wait for them
-  // too (the gridder issued at 0.90 of its instruction stream, round 6).
-  const long long items = static_cast<long long>(g.nr_timesteps) * C;
-  const float4 *vis4 = reinterpret_cast<const float4 *>(visibilities) +
-                       g.time_offset * C * 2;
-  float pidx[NQ];
-  for (long long i0 = 0; i0 < items; i0 += kSeqStage) {
-    const int ne = static_cast<int>(items - i0 < kSeqStage ? items - i0 : kSeqStage);
-    __syncthreads();  // the previous block's readers are done
-    for (int e = threadIdx.x; e < ne; e += kSeqBlock) {
-      const long long it = i0 + e;
-      const int t = static_cast<int>(it / C), c = static_cast<int>(it % C);
-      st_vis[2 * e] = vis4[it * 2];
-      st_vis[2 * e + 1] = vis4[it * 2 + 1];
-      const idg::UVWCoordinate<float> c3 = uvw[g.time_offset + t];
-      st_uvwk[e] = make_float4(c3.u, c3.v, c3.w, wavenumbers[c]);
-    }
-    __syncthreads();
-    int ch = static_cast<int>(i0 % C);
-    for (int e = 0; e < ne; ++e) {
-      const float4 uvwk = st_uvwk[e];
-      const float4 va = st_vis[2 * e], vb = st_vis[2 * e + 1];
-      if (ch == 0 || e == 0) {  // a new timestep (or block): phase_index
-#pragma unroll
-        for (int i = 0; i < NQ; ++i)
-          pidx[i] = fma_(uvwk.z, n[i], fma_(uvwk.x, l[i], uvwk.y * m[i]));
-      }
-      ch = ch + 1 == C ? 0 : ch + 1;
-      const float k = uvwk.w;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const float ph = fma_(-pidx[i], k, po[i]);
-        float sn, cs;
-        idg::sincosf_glibc_dev(ph, &sn, &cs, win);
-        if constexpr (MIRROR) {
-          // the mirror's own phase, formed as the reference forms it; where
-          // it is the exact negation (every lane of every wave on the
-          // benchmark data) one sincosf and one set of products serve both
-          const float phm = fma_(-pidx[NP + i], k, po[NP + i]);
-          const bool neg = fbits(phm) == (fbits(ph) ^ 0x80000000u);
-          if (__all(neg)) {
-            mac_ref_pair(acc[i], acc[NP + i], va, vb, cs, sn);
-          } else {
-            float snm = -sn, csm = cs;
-            if (!neg) idg::sincosf_glibc_dev(phm, &snm, &csm, win);
-            mac_ref(acc[i], va, vb, cs, sn);
-            mac_ref(acc[NP + i], va, vb, csm, snm);
-          }
-        } else {
-          mac_ref(acc[i], va, vb, cs, sn);
-        }
-      }
-    }
+  __device__ __forceinline__ void mirror(float phm, bool neg, float sn,
+                                         float cs, float *snm,
+                                         float *csm) const {
+    *snm = -sn;
+    *csm = cs;
+    if (!neg) idg::sincosf_glibc_dev(phm, snm, csm, win);
   }
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    if (base[i % NP] >= nbase) continue;
-    const int p = i < NP ? base[i] : npix - 1 - base[i - NP];
-    seq_store_pixel(acc[i], p, S, npix, g, nr_stations, spheroidal, aterms,
-                    out);
-  }
-}
+};
 
 }  // namespace
 
@@ -175,11 +104,8 @@ __global__ void __launch_bounds__(kSeqBlock)
   const SubgridSetup g = setup_subgrid(metadata, s, grid_size, S, image_size,
                                        w_step_in_lambda);
   float2 *out = subgrids + static_cast<size_t>(s) * 4 * npix;
-  bool w_nonzero = false;
-  for (int t = tid; t < g.nr_timesteps; t += kSeqBlock)
-    w_nonzero |= uvw[g.time_offset + t].w != 0.0f;
-  const bool mirror = __syncthreads_or(w_nonzero) == 0 && S % 2 == 0 &&
-                      g.w_offset == 0.0f;
+  const GlibcPhasor phasor{win};
+  const bool mirror = mirror_eligible(g, S, uvw, tid);
   if (mirror) {
     constexpr int NP = 2;
     const int half = npix / 2;
@@ -187,10 +113,10 @@ __global__ void __launch_bounds__(kSeqBlock)
       int base[NP];
 #pragma unroll
       for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
-      seq_grid_pixels<NP, true>(base, half, S, npix, image_size, g,
-                                nr_channels, nr_stations, uvw, wavenumbers,
-                                visibilities, spheroidal, aterms, out, win,
-                                st_vis, st_uvwk);
+      order_grid_pixels<NP, true>(base, half, S, npix, image_size, g,
+                                  nr_channels, nr_stations, uvw, wavenumbers,
+                                  visibilities, spheroidal, aterms, out,
+                                  st_vis, st_uvwk, phasor);
     }
     return;
   }
@@ -199,10 +125,10 @@ __global__ void __launch_bounds__(kSeqBlock)
     int base[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) base[i] = tile + i * kSeqBlock + tid;
-    seq_grid_pixels<NP, false>(base, npix, S, npix, image_size, g,
-                               nr_channels, nr_stations, uvw, wavenumbers,
-                               visibilities, spheroidal, aterms, out, win,
-                               st_vis, st_uvwk);
+    order_grid_pixels<NP, false>(base, npix, S, npix, image_size, g,
+                                 nr_channels, nr_stations, uvw, wavenumbers,
+                                 visibilities, spheroidal, aterms, out,
+                                 st_vis, st_uvwk, phasor);
   }
 }
 
@@ -363,25 +289,17 @@ __global__ void __launch_bounds__(kSeqBlock)
 
 // The sequential kernels of subgrid size S (32, 64, or 0 = runtime S).
 const void *sequential_gridder(int S) {
-  switch (S) {
-    case 32: return reinterpret_cast<const void *>(
-        &kernel_gridder_sequential_mi355x<32>);
-    case 64: return reinterpret_cast<const void *>(
-        &kernel_gridder_sequential_mi355x<64>);
-    default: return reinterpret_cast<const void *>(
-        &kernel_gridder_sequential_mi355x<0>);
-  }
+  return kernel_for_size(S, [](auto s) {
+    return reinterpret_cast<const void *>(
+        &kernel_gridder_sequential_mi355x<decltype(s)::value>);
+  });
 }
 
 const void *sequential_degridder(int S) {
-  switch (S) {
-    case 32: return reinterpret_cast<const void *>(
-        &kernel_degridder_sequential_mi355x<32>);
-    case 64: return reinterpret_cast<const void *>(
-        &kernel_degridder_sequential_mi355x<64>);
-    default: return reinterpret_cast<const void *>(
-        &kernel_degridder_sequential_mi355x<0>);
-  }
+  return kernel_for_size(S, [](auto s) {
+    return reinterpret_cast<const void *>(
+        &kernel_degridder_sequential_mi355x<decltype(s)::value>);
+  });
 }
 
 int sequential_block() { return kSeqBlock; }

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -233,6 +234,24 @@ bool two_kernel_form(int nr_subgrids, const Options &opt = Options());
 constexpr int kTailMinChannels = 16;
 int precision_for(Direction dir, const Problem &p,
                   const Options &opt = Options());
+
+// The kernels are built for S = 32, S = 64 and a runtime S (template argument
+// 0).  kernel_for_size: pick(std::integral_constant<int, 32 | 64 | 0>) for a
+// subgrid size, pick returning the address of that instantiation.
+template <typename Pick>
+const void *kernel_for_size(int subgrid_size, Pick pick) {
+  switch (subgrid_size) {
+    case 32: return pick(std::integral_constant<int, 32>{});
+    case 64: return pick(std::integral_constant<int, 64>{});
+    default: return pick(std::integral_constant<int, 0>{});
+  }
+}
+// The matching kernel name, prefix "_s32" / "_s64" / "_generic": string
+// literals, because idg_kernel_name hands the pointer out.
+#define IDG_SIZE_NAME(prefix, subgrid_size)   \
+  ((subgrid_size) == 32   ? prefix "_s32"     \
+   : (subgrid_size) == 64 ? prefix "_s64"     \
+                          : prefix "_generic")
 
 // Defined in the kernel TUs.
 KernelChoice select_gridder(const Problem &p, const Options &opt = Options());
