@@ -234,6 +234,70 @@ int idg_splitter_fft_launch(int nr_subgrids, int grid_size, int subgrid_size,
                             const idg_cfloat_t *grid, idg_cfloat_t *subgrids,
                             void *stream);
 
+/* ---- grid <-> image ----------------------------------------
+ * The steps between the uv grid and the image, in this library's sign
+ * convention (the degridder's phase +i (k (u l + v m + w n) - offset), the
+ * gridder its adjoint).  Image: [4][grid_size][grid_size] complex64,
+ * correlation-planar like the grid; pixel (y, x) stands for
+ *   l = (x - grid_size/2) * image_size / grid_size,
+ *   m = (y - grid_size/2) * image_size / grid_size,  n = 1 - sqrt(1 - l^2 - m^2).
+ * grid_size: a power of two in [64, 4096]; 1 <= nr_w_layers <= 16383 (the
+ * 4 nr_w_layers planes are one launch's grid); else IDG_E_INVALID_ARGUMENT.
+ * Device pointers, asynchronous on `stream`; no scratch is needed beyond the
+ * grid itself, so a launch allocates nothing.  None of the four entries has
+ * a reference counterpart (the reference stops at subgrids).
+ */
+
+/* In-place 2-D DFT of nr_planes planes of [grid_size][grid_size] complex64,
+ * the definition of idg_subgrid_fft_launch: out[k][l] = scale * sum in[y][x] *
+ * exp(sign * 2 pi i (k y + l x) / grid_size); sign = +1 or -1; no shift.
+ * No reference counterpart. */
+int idg_grid_fft_launch(int grid_size, int nr_planes, int sign, float scale,
+                        idg_cfloat_t *planes, void *stream);
+
+/* image[pol][y][x] = correction[y][x] * sum_z exp(-2 pi i w_step_in_lambda
+ * (z + 0.5) n) * sum_{Y,X} grid[z][pol][Y][X] * exp(-2 pi i ((X - G/2)(x - G/2)
+ * + (Y - G/2)(y - G/2)) / G): the centred grid FFT, the w-stacking phasor,
+ * the sum over the layers and the correction (real [G][G]; NULL = 1).  With
+ * the grid that idg_adder_launch fills from
+ * idg_gridder_fft_launch this is S^2 taper(l, m) times the direct sum
+ * sum_{row,c} A1^H V A2 exp(-i k_c (u l + v m + w n)) (S = the subgrid size,
+ * taper = idg_taper_to_image): pass correction = 1 / (S^2 taper) for the
+ * image itself.  DESTROYS the grid (the transform's passes run in place).
+ * No reference counterpart. */
+int idg_grid_to_image_launch(int grid_size, int nr_w_layers, float image_size,
+                             float w_step_in_lambda, const float *correction,
+                             idg_cfloat_t *grid, idg_cfloat_t *image,
+                             void *stream);
+
+/* The exact adjoint of idg_grid_to_image_launch: grid[z][pol][Y][X] =
+ * sum_{y,x} exp(+2 pi i ((X - G/2)(x - G/2) + (Y - G/2)(y - G/2)) / G) *
+ * exp(+2 pi i w_step_in_lambda (z + 0.5) n) * correction[y][x] *
+ * image[pol][y][x]; every one of the nr_w_layers layers is overwritten.
+ * With correction = 1 / taper, idg_splitter_fft_launch and
+ * idg_degridder_launch then predict V = sum_{y,x} A1 image A2^H
+ * exp(+i k_c (u l + v m + w n)).  No reference counterpart. */
+int idg_image_to_grid_launch(int grid_size, int nr_w_layers, float image_size,
+                             float w_step_in_lambda, const float *correction,
+                             const idg_cfloat_t *image, idg_cfloat_t *grid,
+                             void *stream);
+
+/* The taper as the image sees it (host pointers, no device needed):
+ * out[grid_size][grid_size] (double) = the separable trigonometric interpolant of
+ * spheroidal[S][S], whose samples sit at the subgrid's half-pixel-centred
+ * positions (p + 0.5 - S/2) / S of the field of view, evaluated at the image
+ * pixels' (x - grid_size/2) / grid_size; the Nyquist term is split
+ * symmetrically, so the result is real.  S/2 and grid_size/2 are integer
+ * divisions, as in the gridder's own pixel coordinates (reference
+ * app/common/math.hpp:9-13): for an odd S the samples sit at p + 0.5 -
+ * floor(S/2), half a pixel off the field centre, where the gridder puts
+ * them, and there is no Nyquist term.  Summed directly in double,
+ * O(G S (S + G)).  The caller inverts it (and decides where it is too close
+ * to 0 to invert).  subgrid_size, grid_size >= 1, else
+ * IDG_E_INVALID_ARGUMENT.  No reference counterpart. */
+int idg_taper_to_image(int subgrid_size, int grid_size,
+                       const float *spheroidal, double *out);
+
 /* ---- synthetic observation (app/common/init.cpp:4-180) -------------------
  * Exactly the reference harness' inputs: srand(0), then the initialize_*
  * generators in harness order.  nr_subgrids = nr_stations*(nr_stations-1)/2

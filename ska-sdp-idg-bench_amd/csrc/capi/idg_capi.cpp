@@ -294,6 +294,109 @@ int idg_splitter_fft_launch(int nr_subgrids, int grid_size, int subgrid_size,
                   "idg_splitter_fft_launch");
 }
 
+int idg_grid_fft_launch(int grid_size, int nr_planes, int sign, float scale,
+                        idg_cfloat_t *planes, void *stream) {
+  if (!idg_mi355x::grid_fft_supported(grid_size) || nr_planes < 0 ||
+      (sign != 1 && sign != -1))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_grid_fft_launch: grid_size a power of two in [64, 4096] "
+                "(got " + std::to_string(grid_size) +
+                    "), nr_planes >= 0, sign = +1 or -1");
+  if (nr_planes > 0 && planes == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_grid_fft_launch: null buffer");
+  return from_hip(idg_mi355x::launch_grid_fft(
+                      grid_size, nr_planes, sign, scale, planes,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_grid_fft_launch");
+}
+
+namespace {
+int check_image_step(const char *what, int grid_size, int nr_w_layers,
+                     float image_size, const void *grid, const void *image) {
+  if (!idg_mi355x::grid_fft_supported(grid_size) || nr_w_layers < 1 ||
+      nr_w_layers > 16383 || !(image_size > 0.0f))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                std::string(what) +
+                    ": grid_size a power of two in [64, 4096] (got " +
+                    std::to_string(grid_size) +
+                    "), 1 <= nr_w_layers <= 16383, image_size > 0");
+  if (grid == nullptr || image == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, std::string(what) + ": null buffer");
+  return IDG_OK;
+}
+}  // namespace
+
+int idg_grid_to_image_launch(int grid_size, int nr_w_layers, float image_size,
+                             float w_step_in_lambda, const float *correction,
+                             idg_cfloat_t *grid, idg_cfloat_t *image,
+                             void *stream) {
+  if (int rc = check_image_step("idg_grid_to_image_launch", grid_size,
+                                nr_w_layers, image_size, grid, image))
+    return rc;
+  return from_hip(idg_mi355x::launch_grid_to_image(
+                      grid_size, nr_w_layers, image_size, w_step_in_lambda,
+                      correction, grid, image,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_grid_to_image_launch");
+}
+
+int idg_image_to_grid_launch(int grid_size, int nr_w_layers, float image_size,
+                             float w_step_in_lambda, const float *correction,
+                             const idg_cfloat_t *image, idg_cfloat_t *grid,
+                             void *stream) {
+  if (int rc = check_image_step("idg_image_to_grid_launch", grid_size,
+                                nr_w_layers, image_size, grid, image))
+    return rc;
+  return from_hip(idg_mi355x::launch_image_to_grid(
+                      grid_size, nr_w_layers, image_size, w_step_in_lambda,
+                      correction, image, grid,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_image_to_grid_launch");
+}
+
+int idg_taper_to_image(int subgrid_size, int grid_size,
+                       const float *spheroidal, double *out) {
+  const int S = subgrid_size, G = grid_size;
+  if (S < 1 || G < 1 || spheroidal == nullptr || out == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_taper_to_image: subgrid_size >= 1, grid_size >= 1 and "
+                "non-null buffers required");
+  // d[j][p]: the periodic interpolation kernel from sample p, at (p + 0.5 -
+  // S/2) subgrid pixels, to image pixel j, at (j - G/2) S / G of them;
+  // frequencies |k| < S/2 whole, the Nyquist pair (even S) as one cosine
+  const double two_pi = 6.283185307179586476925287;
+  std::vector<double> d(static_cast<size_t>(G) * S);
+  for (int j = 0; j < G; ++j)
+    for (int p = 0; p < S; ++p) {
+      const double delta = static_cast<double>(j - G / 2) * S / G -
+                           (static_cast<double>(p) + 0.5 - S / 2);
+      double sum = 1.0;
+      for (int k = 1; 2 * k < S; ++k)
+        sum += 2.0 * std::cos(two_pi * k * delta / S);
+      if (S % 2 == 0) sum += std::cos(0.5 * two_pi * delta);
+      d[static_cast<size_t>(j) * S + p] = sum / S;
+    }
+  // out = d taper d^T, the x sum first
+  std::vector<double> rows(static_cast<size_t>(S) * G);
+  for (int py = 0; py < S; ++py)
+    for (int j = 0; j < G; ++j) {
+      double sum = 0.0;
+      for (int px = 0; px < S; ++px)
+        sum += static_cast<double>(spheroidal[py * S + px]) *
+               d[static_cast<size_t>(j) * S + px];
+      rows[static_cast<size_t>(py) * G + j] = sum;
+    }
+  for (int i = 0; i < G; ++i)
+    for (int j = 0; j < G; ++j) {
+      double sum = 0.0;
+      for (int py = 0; py < S; ++py)
+        sum += d[static_cast<size_t>(i) * S + py] *
+               rows[static_cast<size_t>(py) * G + j];
+      out[static_cast<size_t>(i) * G + j] = sum;
+    }
+  return IDG_OK;
+}
+
 int idg_c_run_gridder(int nr_subgrids, int grid_size, int subgrid_size,
                       float image_size, float w_step_in_lambda,
                       int nr_channels, int nr_stations, const idg_uvw_t *uvw,

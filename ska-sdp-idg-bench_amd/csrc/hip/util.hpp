@@ -376,6 +376,25 @@ hipError_t launch_splitter_fft(int nr_subgrids, int grid_size,
                                const void *d_metadata, const void *d_grid,
                                void *d_subgrids, hipStream_t stream);
 
+// Grid <-> image (kernels/image_mi355x.hip.cpp).  grid_size:
+// a power of two in [64, 4096] (grid_fft_supported), else
+// hipErrorInvalidValue.  launch_grid_fft: in-place 2-D DFT of nr_planes
+// planes, the definition of launch_subgrid_fft.  launch_grid_to_image
+// destroys the grid (the transform runs in place); launch_image_to_grid
+// overwrites every layer.  d_correction: [G][G] floats or null (1).  None of
+// them needs scratch beyond the grid.
+bool grid_fft_supported(int grid_size);
+hipError_t launch_grid_fft(int grid_size, int nr_planes, int sign, float scale,
+                           void *d_planes, hipStream_t stream);
+hipError_t launch_grid_to_image(int grid_size, int nr_w_layers,
+                                float image_size, float w_step_in_lambda,
+                                const float *d_correction, void *d_grid,
+                                void *d_image, hipStream_t stream);
+hipError_t launch_image_to_grid(int grid_size, int nr_w_layers,
+                                float image_size, float w_step_in_lambda,
+                                const float *d_correction, const void *d_image,
+                                void *d_grid, hipStream_t stream);
+
 // Perf entry shared by p_run_gridder_/p_run_degridder_: env-configured
 // problem, synthetic inputs, timed launches.  Returns seconds per launch.
 double run_performance(Direction dir, const void *func, std::string name,

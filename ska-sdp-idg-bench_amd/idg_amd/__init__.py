@@ -15,7 +15,9 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   p_run_degridder, p_run_gridder,
                   release_workspaces,
                   splitter_fft_launch, splitter_launch, subgrid_fft_launch,
-                  validate_metadata)
+                  validate_metadata,
+                  grid_fft_launch, grid_to_image, image_to_grid, invert,
+                  predict, taper_to_image)
 from ._lib import LIB_PATH, OptionsStruct, PlanParamsStruct
 from . import shard
 
@@ -30,4 +32,6 @@ __all__ = [
     "subgrid_fft_launch",
     "validate_metadata", "LIB_PATH", "shard", "Options", "OptionsStruct",
     "auto_selected", "plan", "plan_launch", "PlanParamsStruct",
+    "grid_fft_launch", "grid_to_image", "image_to_grid", "invert", "predict",
+    "taper_to_image",
 ]

@@ -69,6 +69,10 @@ SIGNATURES = {
     "idg_auto_selected": (_I, [_I, _I, _P, _P, _P]),
     "idg_plan": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I]),
     "idg_plan_launch": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "idg_grid_fft_launch": (_I, [_I, _I, _I, _F, _P, _P]),
+    "idg_grid_to_image_launch": (_I, [_I, _I, _F, _F, _P, _P, _P, _P]),
+    "idg_image_to_grid_launch": (_I, [_I, _I, _F, _F, _P, _P, _P, _P]),
+    "idg_taper_to_image": (_I, [_I, _I, _P, _P]),
 }
 
 

@@ -12,6 +12,7 @@ Errors: where the reference's C++ entries abort the process (hipCheck ->
 exit, app/HIP/util.cpp:5-15), these raise IdgError carrying the status code
 and message.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -638,6 +639,176 @@ def plan_launch(grid_size, subgrid_size, image_size, w_step_in_lambda, uvw,
         capacity, _dev_ptr(counts, "counts"), _stream_handle(stream)),
         "plan_launch")
     return metadata, counts
+
+
+# ---------------------------------------------------------------------------
+# Grid <-> image (not in the reference): the G x G grid FFT
+# with the centre shifts inside its passes, and the w-stacking phasor, the
+# sum over the w layers and the taper correction in one launch beside it.
+#   invert:  grid_onto -> grid_to_image      predict: image_to_grid -> degrid_from
+# ---------------------------------------------------------------------------
+MAX_W_LAYERS = 16383    # 4 planes per layer are one launch's grid y (65,535)
+
+
+def _grid_size_ok(G):
+    if not (64 <= G <= 4096 and G & (G - 1) == 0):
+        raise ValueError(f"grid_size must be a power of two in [64, 4096], "
+                         f"got {G}")
+
+
+def _image_extents(grid_size, nr_w_layers, correction, grid, image):
+    import torch
+    G = grid_size
+    _grid_size_ok(G)
+    if nr_w_layers < 1:
+        raise ValueError("nr_w_layers must be >= 1")
+    if nr_w_layers > MAX_W_LAYERS:
+        raise ValueError(f"nr_w_layers must be <= {MAX_W_LAYERS}")
+    if grid.numel() != nr_w_layers * 4 * G * G * 2:
+        raise ValueError(f"grid must be [{nr_w_layers}][4][{G}][{G}][2] "
+                         "float32")
+    if image.numel() != 4 * G * G * 2:
+        raise ValueError(f"image must be [4][{G}][{G}][2] float32")
+    if correction is None:
+        return None
+    if correction.numel() != G * G:
+        raise ValueError(f"correction must be [{G}][{G}] float32")
+    return _dev_ptr(correction, "correction", torch.float32)
+
+
+def grid_fft_launch(planes, sign, scale=1.0, stream=None):
+    """In-place 2-D DFT of every [G][G] plane of a float32 [..., G, G, 2]
+    tensor, the definition of subgrid_fft_launch: out[k][l] = scale * sum
+    in[y][x] exp(sign 2 pi i (k y + l x) / G); no shift.  G: a power of two
+    in [64, 4096]."""
+    import torch
+    if planes.dim() < 3 or planes.shape[-1] != 2 or \
+            planes.shape[-2] != planes.shape[-3]:
+        raise ValueError("planes must be [..., G, G, 2] float32")
+    G = int(planes.shape[-2])
+    _grid_size_ok(G)
+    if sign not in (1, -1):
+        raise ValueError("sign must be +1 or -1")
+    _check(lib.idg_grid_fft_launch(
+        G, planes.numel() // (2 * G * G), int(sign), float(scale),
+        _dev_ptr(planes, "planes", torch.float32), _stream_handle(stream)),
+        "grid_fft_launch")
+
+
+def grid_to_image(grid_size, image_size, w_step_in_lambda, grid, image=None,
+                  nr_w_layers=1, correction=None, stream=None):
+    """uv grid [W, 4, G, G, 2] float32 -> image [4, G, G, 2] float32
+    (idg_grid_to_image_launch): image = correction * sum_z conj(w phasor of
+    layer z) * the centred DFT (sign -1, unscaled) of grid[z].  DESTROYS the
+    grid.  correction: float32 [G, G] or None (1).  Returns the image."""
+    import torch
+    if image is None:
+        image = torch.empty((4, grid_size, grid_size, 2), dtype=torch.float32,
+                            device=grid.device)
+    cptr = _image_extents(grid_size, nr_w_layers, correction, grid, image)
+    _check(lib.idg_grid_to_image_launch(
+        grid_size, nr_w_layers, image_size, w_step_in_lambda, cptr,
+        _dev_ptr(grid, "grid", torch.float32),
+        _dev_ptr(image, "image", torch.float32), _stream_handle(stream)),
+        "grid_to_image")
+    return image
+
+
+def image_to_grid(grid_size, image_size, w_step_in_lambda, image, grid=None,
+                  nr_w_layers=1, correction=None, stream=None):
+    """The exact adjoint of grid_to_image (idg_image_to_grid_launch): every
+    layer of grid [W, 4, G, G, 2] is overwritten.  Returns the grid."""
+    import torch
+    if grid is None:
+        grid = torch.empty((nr_w_layers, 4, grid_size, grid_size, 2),
+                           dtype=torch.float32, device=image.device)
+    cptr = _image_extents(grid_size, nr_w_layers, correction, grid, image)
+    _check(lib.idg_image_to_grid_launch(
+        grid_size, nr_w_layers, image_size, w_step_in_lambda, cptr,
+        _dev_ptr(image, "image", torch.float32),
+        _dev_ptr(grid, "grid", torch.float32), _stream_handle(stream)),
+        "image_to_grid")
+    return grid
+
+
+def taper_to_image(subgrid_size, grid_size, spheroidal):
+    """The [S, S] taper as the image sees it (idg_taper_to_image; host, no
+    device needed): float64 [G, G], the separable trigonometric interpolant
+    of the taper at the image pixels.  correction = 1 / this as float32,
+    masked where the caller chooses."""
+    sph = np.asarray(spheroidal)
+    if sph.shape != (subgrid_size, subgrid_size):
+        raise ValueError(f"spheroidal must be [{subgrid_size}]"
+                         f"[{subgrid_size}]")
+    out = np.empty((max(grid_size, 0), max(grid_size, 0)), np.float64)
+    _check(lib.idg_taper_to_image(
+        subgrid_size, grid_size, _np_ptr(sph, np.float32, "spheroidal"),
+        out.ctypes.data_as(ctypes.c_void_p)), "taper_to_image")
+    return out
+
+
+def _on_stream(stream):
+    """torch's current stream set to `stream` (None: left as it is)."""
+    import torch
+    return (torch.cuda.stream(stream) if stream is not None
+            else contextlib.nullcontext())
+
+
+def invert(nr_subgrids, grid_size, subgrid_size, image_size,
+           w_step_in_lambda, nr_channels, nr_stations, uvw, wavenumbers,
+           visibilities, spheroidal, aterms, metadata, grid=None,
+           nr_w_layers=1, subgrids=None, stream=None, options=None,
+           correction=None, image=None):
+    """Visibilities -> dirty image [4, G, G, 2] float32: grid_onto, then
+    grid_to_image.  The exact adjoint of predict; not divided by the number
+    of visibilities (one unit visibility with identity A-terms gives modulus
+    ~1 everywhere).  grid: None (a zeroed grid is made) or a [W, 4, G, G, 2]
+    grid to accumulate onto; it is destroyed.  correction: float32 [G, G]
+    (1 / taper_to_image) or None; the 1 / S^2 that undoes the gridding FFT's
+    normalisation is folded into it here."""
+    import torch
+    if correction is not None and correction.numel() != grid_size * grid_size:
+        raise ValueError(f"correction must be [{grid_size}][{grid_size}] "
+                         "float32")
+    inv = 1.0 / float(subgrid_size * subgrid_size)
+    dev = visibilities.device
+    # Everything torch fills or allocates here -- the zeroed grid, the scaled
+    # correction, the scratch and the image -- is made with `stream` current,
+    # so that the fills are ordered before the kernels enqueued on it.
+    with _on_stream(stream):
+        if grid is None:
+            grid = torch.zeros((nr_w_layers, 4, grid_size, grid_size, 2),
+                               dtype=torch.float32, device=dev)
+        if correction is None:
+            scaled = torch.full((grid_size, grid_size), inv,
+                                dtype=torch.float32, device=dev)
+        else:
+            scaled = (correction.to(torch.float32) * inv).contiguous()
+        grid_onto(nr_subgrids, grid_size, subgrid_size, image_size,
+                  w_step_in_lambda, nr_channels, nr_stations, uvw,
+                  wavenumbers, visibilities, spheroidal, aterms, metadata,
+                  grid, nr_w_layers, subgrids, stream, options)
+        return grid_to_image(grid_size, image_size, w_step_in_lambda, grid,
+                             image, nr_w_layers, scaled, stream)
+
+
+def predict(nr_subgrids, grid_size, subgrid_size, image_size,
+            w_step_in_lambda, nr_channels, nr_stations, uvw, wavenumbers,
+            visibilities, spheroidal, aterms, metadata, image, grid=None,
+            nr_w_layers=1, subgrids=None, stream=None, options=None,
+            correction=None):
+    """Model image [4, G, G, 2] float32 -> visibilities (written for every
+    row the metadata covers): image_to_grid, then degrid_from.  One unit
+    pixel predicts visibilities of modulus ~1.  grid: scratch [W, 4, G, G, 2]
+    or None.  Returns the grid."""
+    with _on_stream(stream):    # the scratch is allocated for `stream`
+        grid = image_to_grid(grid_size, image_size, w_step_in_lambda, image,
+                             grid, nr_w_layers, correction, stream)
+        degrid_from(nr_subgrids, grid_size, subgrid_size, image_size,
+                    w_step_in_lambda, nr_channels, nr_stations, uvw,
+                    wavenumbers, visibilities, spheroidal, aterms, metadata,
+                    grid, nr_w_layers, subgrids, stream, options)
+    return grid
 
 
 # ---------------------------------------------------------------------------
