@@ -317,7 +317,8 @@ int idg_generate(int nr_stations, int nr_timeslots, int nr_timesteps,
 
 /* ---- workspaces -----------------------------------------------------------
  * The device entries keep their scratch (the two-kernel form's subgrid queue,
- * the adder's home sort and segment lists) cached per (device, stream), so a
+ * the adder's home sort and segment lists, the plan's counts, the weight
+ * steps' partial sums) cached per (device, stream), so a
  * launch makes no allocation.  idg_release_workspaces frees the cache of
  * `stream` on the current device (all != 0: of every stream of the current
  * device).  The stream(s) must be idle (their work complete): call it before
@@ -519,6 +520,118 @@ int idg_plan_launch(const idg_plan_params_t *params, int nr_baselines,
                     const idg_uvw_t *uvw, int nr_channels,
                     const float *wavenumbers, idg_metadata_t *metadata,
                     int capacity, int32_t counts[2], void *stream);
+
+/* ---- imaging weights -------------------------------------------
+ * The step between "uvw, visibilities and weights" and a normalised dirty
+ * image and its PSF: the uv sampling density of the samples the gridder will
+ * grid, the (a, b) of a weighting scheme, and the imaging weights
+ * f = w / (a + b D).  No reference counterpart (the reference stops at
+ * subgrids); each entry has a host form (host pointers, no device needed)
+ * and a _launch form (device pointers, asynchronous on `stream`, nothing read
+ * back) that produce the same bytes, except the two double sums noted below.
+ *
+ * weights: float32 [rows][nr_channels], one weight per row and channel,
+ * shared by the four correlations; a flag is a weight of 0.  Only the samples
+ * a subgrid covers count (rows time_offset .. time_offset + nr_timesteps - 1
+ * of each record, indexed as for the gridder); other rows are neither read
+ * nor written.
+ *
+ * Cell of a sample: X = floorf(u * s_c + 0.5f) + grid_size / 2 (Y from v),
+ * s_c = wavenumbers[c] * (image_size / 2 pi): the nearest cell of the grid
+ * idg_grid_to_image_launch transforms; w and the w layer play no part.
+ * Quantised weight: q = (uint64) rintf(w * 2^-quantum_log2) for a finite
+ * w > 0 whose scaled value is below 2^40, else 0.  A sample with q = 0, or
+ * whose cell is not finite or outside the grid, is flagged: nothing in the
+ * density, imaging weight 0, weighted visibility literal zeros.
+ * density: uint64 [grid_size][grid_size]; density[Y][X] = the sum of q over
+ * the covered samples in that cell -- exact, whatever the order.  THE CALLER
+ * KEEPS EVERY CELL'S SUM BELOW 2^62 (with q < 2^40 that is 2^22 samples of
+ * the largest weight in one cell); the host entries check it.
+ * D at a cell = (float) n * 2^quantum_log2 with n = density[Y][X], plus
+ * density[G - Y][G - X] when `hermitian` is set and that cell is inside the
+ * grid (X, Y >= 1): the centre cell counts twice, row 0 and column 0 have no
+ * mirror.
+ *
+ * struct_size = sizeof(idg_weight_params_t), with the rules of idg_options_t.
+ * The fields are taken as they are (0 is quantum 1, hermitian off, natural):
+ * set quantum_log2 = IDG_WEIGHT_QUANTUM_LOG2_DEFAULT and hermitian = 1 for
+ * the usual case.  IDG_E_INVALID_ARGUMENT: a bad struct_size, grid_size < 1
+ * or > 16384, quantum_log2 outside [-64, 64], an unknown scheme, a non-finite
+ * image_size or robust, nr_subgrids < 0, nr_channels < 1, subgrid_size < 1,
+ * a null buffer, a density cell at or above 2^62 (host forms).
+ * IDG_E_OUT_OF_BOUNDS: a record's rows outside [0, uvw_rows) (host forms; the
+ * _launch forms trust the metadata, use idg_validate_metadata). */
+#define IDG_WEIGHT_NATURAL 0 /* a = 1, b = 0: f = w                           */
+#define IDG_WEIGHT_UNIFORM 1 /* a = 0, b = 1: f = w / D                       */
+#define IDG_WEIGHT_BRIGGS 2  /* a = 1, b = (float)((5 * 10^-robust)^2 *
+                                sum D / sum D^2), the sums over all cells in
+                                double; b = 0 for an empty density            */
+#define IDG_WEIGHT_QUANTUM_LOG2_DEFAULT (-20)
+
+typedef struct idg_weight_params_t {
+  uint32_t struct_size; /* sizeof(idg_weight_params_t)                       */
+  int32_t grid_size;
+  float image_size;
+  int32_t quantum_log2; /* weights are counted in units of 2^quantum_log2    */
+  int32_t hermitian;    /* != 0: D counts the mirror cell too                */
+  int32_t scheme;       /* IDG_WEIGHT_* (idg_weight_scheme*)                 */
+  float robust;         /* IDG_WEIGHT_BRIGGS                                 */
+} idg_weight_params_t;
+
+/* density[Y][X] += the sum of q over the covered samples of that cell: the
+ * entry accumulates, the caller zeroes the buffer, several batches may add to
+ * one density.  nr_subgrids = 0: a no-op.  The host form leaves the density
+ * untouched when it fails.  Device: one workgroup per subgrid sums in an
+ * S x S LDS tile at the subgrid's corner and adds its non-zero cells, and
+ * every sample outside the tile, with 64-bit integer atomics; correct for any
+ * metadata, fastest for a plan's. */
+int idg_weight_density(const idg_weight_params_t *params, int nr_subgrids,
+                       int subgrid_size, int nr_channels,
+                       const idg_metadata_t *metadata, const idg_uvw_t *uvw,
+                       size_t uvw_rows, const float *wavenumbers,
+                       const float *weights, uint64_t *density);
+int idg_weight_density_launch(const idg_weight_params_t *params,
+                              int nr_subgrids, int subgrid_size,
+                              int nr_channels, const idg_metadata_t *metadata,
+                              const idg_uvw_t *uvw, const float *wavenumbers,
+                              const float *weights, uint64_t *density,
+                              void *stream);
+
+/* ab[0] = a, ab[1] = b of params->scheme at this density.  The Briggs sums
+ * run in double: the host form in row-major order, the device form in a
+ * fixed tree (bitwise reproducible run to run; b may differ from the host's
+ * in the last place). */
+int idg_weight_scheme(const idg_weight_params_t *params,
+                      const uint64_t *density, float ab[2]);
+int idg_weight_scheme_launch(const idg_weight_params_t *params,
+                             const uint64_t *density, float ab[2],
+                             void *stream);
+
+/* For every covered sample: imaging_weights[row][c] = f = w / (a + b D) (one
+ * multiply, one add, one correctly rounded divide; 0 for a flagged sample),
+ * out[row][c][pol] = f * visibilities[row][c][pol] (one multiply per
+ * component; literal zeros for a flagged sample; out may be visibilities;
+ * visibilities NULL: (f, 0, 0, f), the PSF's input), and *sum_weights = the
+ * sum of f over the covered samples, in double (host: sequentially; device:
+ * per-subgrid partials and a final sum in fixed orders, reproducible run to
+ * run; nr_subgrids = 0 writes 0).  ab: the two floats idg_weight_scheme*
+ * wrote.  Rows no subgrid covers are left as they were in all three outputs.
+ * The _launch form needs visibilities and out 16-byte aligned. */
+int idg_weight_apply(const idg_weight_params_t *params, int nr_subgrids,
+                     int nr_channels, const idg_metadata_t *metadata,
+                     const idg_uvw_t *uvw, size_t uvw_rows,
+                     const float *wavenumbers, const float *weights,
+                     const uint64_t *density, const float ab[2],
+                     const idg_cfloat_t *visibilities, float *imaging_weights,
+                     idg_cfloat_t *out, double *sum_weights);
+int idg_weight_apply_launch(const idg_weight_params_t *params, int nr_subgrids,
+                            int nr_channels, const idg_metadata_t *metadata,
+                            const idg_uvw_t *uvw, const float *wavenumbers,
+                            const float *weights, const uint64_t *density,
+                            const float ab[2],
+                            const idg_cfloat_t *visibilities,
+                            float *imaging_weights, idg_cfloat_t *out,
+                            double *sum_weights, void *stream);
 
 #ifdef __cplusplus
 }

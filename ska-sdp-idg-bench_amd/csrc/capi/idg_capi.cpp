@@ -5,12 +5,14 @@
 
 #include <cstdio>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "common/plan.hpp"
+#include "common/weight.hpp"
 #include "hip/util.hpp"
 #include "lib-hip.hpp"
 
@@ -170,6 +172,101 @@ int parse_plan(const idg_plan_params_t *params, int nr_baselines,
   g->s0 = g->s1 = g->ws = 0.0f;
   *image_size = v.image_size;
   *inv_w_step = g->use_w ? 1.0f / v.w_step_in_lambda : 0.0f;
+  return IDG_OK;
+}
+
+// idg_weight_params_t (struct_size rules of idg_options_t) and the sizes of a
+// weight call -> weight::Geometry, the scheme and (5 * 10^-robust)^2.
+struct WeightCall {
+  idg_mi355x::weight::Geometry g;
+  int scheme = 0;
+  double briggs_scale = 0.0;
+};
+
+int parse_weight(const idg_weight_params_t *params, int nr_subgrids,
+                 int subgrid_size, int nr_channels, WeightCall *out) {
+  namespace wt = idg_mi355x::weight;
+  if (params == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_params_t: null");
+  const uint32_t size = params->struct_size;
+  if (size < sizeof(uint32_t) || size % 4 != 0 || size > (1u << 16))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_weight_params_t: struct_size " + std::to_string(size) +
+                    " (set it to sizeof(idg_weight_params_t))");
+  idg_weight_params_t v;
+  std::memset(&v, 0, sizeof v);
+  std::memcpy(&v, params, std::min<size_t>(size, sizeof v));
+  const unsigned char *raw = reinterpret_cast<const unsigned char *>(params);
+  for (size_t i = sizeof v; i < size; ++i)
+    if (raw[i] != 0)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "idg_weight_params_t: struct_size " + std::to_string(size) +
+                      " with a field set that this library (struct_size " +
+                      std::to_string(sizeof v) + ") does not know");
+  if (nr_subgrids < 0 || subgrid_size < 1 || nr_channels < 1)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "weight: nr_subgrids >= 0, subgrid_size >= 1 and "
+                "nr_channels >= 1 required");
+  if (v.grid_size < 1 || v.grid_size > 16384)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "weight: 1 <= grid_size <= 16384 required");
+  if (v.quantum_log2 < wt::kQuantumLog2Min ||
+      v.quantum_log2 > wt::kQuantumLog2Max)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "weight: quantum_log2 must lie in [-64, 64]");
+  if (v.scheme != IDG_WEIGHT_NATURAL && v.scheme != IDG_WEIGHT_UNIFORM &&
+      v.scheme != IDG_WEIGHT_BRIGGS)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "weight: unknown scheme " + std::to_string(v.scheme));
+  if (!std::isfinite(v.image_size) || !std::isfinite(v.robust))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "weight: image_size and robust must be finite");
+  out->g.grid_size = v.grid_size;
+  out->g.quantum_log2 = v.quantum_log2;
+  out->g.hermitian = v.hermitian != 0 ? 1 : 0;
+  out->g.cells = wt::cells_of(v.image_size);
+  out->scheme = v.scheme;
+  const double r = 5.0 * std::pow(10.0, -static_cast<double>(v.robust));
+  out->briggs_scale = r * r;
+  return IDG_OK;
+}
+static_assert(IDG_WEIGHT_NATURAL == idg_mi355x::weight::kNatural &&
+                  IDG_WEIGHT_UNIFORM == idg_mi355x::weight::kUniform &&
+                  IDG_WEIGHT_BRIGGS == idg_mi355x::weight::kBriggs,
+              "idg_weight_params_t scheme values are weight:: values");
+
+// Row of timestep 0 of subgrid s (include/idg_mi355x.h).
+long long weight_row0(const idg_metadata_t *md, int s) {
+  return (static_cast<long long>(md[s].baseline_offset) -
+          md[0].baseline_offset) +
+         md[s].time_offset;
+}
+
+// Every record's rows inside [0, uvw_rows).
+int check_weight_rows(int nr_subgrids, size_t uvw_rows,
+                      const idg_metadata_t *md) {
+  for (int s = 0; s < nr_subgrids; ++s) {
+    const long long t0 = weight_row0(md, s);
+    if (md[s].nr_timesteps < 0 || t0 < 0 ||
+        t0 + md[s].nr_timesteps > static_cast<long long>(uvw_rows))
+      return fail(IDG_E_OUT_OF_BOUNDS,
+                  "subgrid " + std::to_string(s) + ": timesteps [" +
+                      std::to_string(t0) + ", " +
+                      std::to_string(t0 + md[s].nr_timesteps) +
+                      ") outside uvw/weight rows [0, " +
+                      std::to_string(uvw_rows) + ")");
+  }
+  return IDG_OK;
+}
+
+int check_density_cells(const idg_mi355x::weight::Geometry &g,
+                        const uint64_t *density) {
+  const size_t cells = static_cast<size_t>(g.grid_size) * g.grid_size;
+  for (size_t i = 0; i < cells; ++i)
+    if (density[i] >= idg_mi355x::weight::kCellLimit)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "weight: density cell " + std::to_string(i) +
+                      " is at or above 2^62");
   return IDG_OK;
 }
 
@@ -735,6 +832,196 @@ int idg_plan_launch(const idg_plan_params_t *params, int nr_baselines,
                       nr_channels, baselines, uvw, wavenumbers, metadata,
                       capacity, counts, static_cast<hipStream_t>(stream)),
                   "idg_plan_launch");
+}
+
+int idg_weight_density(const idg_weight_params_t *params, int nr_subgrids,
+                       int subgrid_size, int nr_channels,
+                       const idg_metadata_t *metadata, const idg_uvw_t *uvw,
+                       size_t uvw_rows, const float *wavenumbers,
+                       const float *weights, uint64_t *density) {
+  namespace wt = idg_mi355x::weight;
+  WeightCall call;
+  if (int rc = parse_weight(params, nr_subgrids, subgrid_size, nr_channels,
+                            &call))
+    return rc;
+  if (nr_subgrids == 0) return IDG_OK;
+  if (!metadata || !uvw || !wavenumbers || !weights || !density)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_density: null buffer");
+  if (int rc = check_weight_rows(nr_subgrids, uvw_rows, metadata)) return rc;
+  if (int rc = check_density_cells(call.g, density)) return rc;
+  const size_t G = static_cast<size_t>(call.g.grid_size), C = nr_channels;
+  // summed on a copy, so that a failure leaves the caller's density alone
+  std::vector<uint64_t> sum(density, density + G * G);
+  for (int s = 0; s < nr_subgrids; ++s) {
+    const size_t row0 = static_cast<size_t>(weight_row0(metadata, s));
+    for (int t = 0; t < metadata[s].nr_timesteps; ++t) {
+      const size_t row = row0 + t;
+      for (size_t c = 0; c < C; ++c) {
+        int x, y;
+        const uint64_t q = wt::sample(call.g, uvw[row].u, uvw[row].v,
+                                      wavenumbers[c], weights[row * C + c],
+                                      &x, &y);
+        if (q == 0) continue;
+        uint64_t &cell = sum[static_cast<size_t>(y) * G + x];
+        cell += q;
+        if (cell >= wt::kCellLimit)
+          return fail(IDG_E_INVALID_ARGUMENT,
+                      "idg_weight_density: the sum of cell (" +
+                          std::to_string(x) + ", " + std::to_string(y) +
+                          ") reaches 2^62");
+      }
+    }
+  }
+  std::memcpy(density, sum.data(), G * G * sizeof(uint64_t));
+  return IDG_OK;
+}
+
+int idg_weight_density_launch(const idg_weight_params_t *params,
+                              int nr_subgrids, int subgrid_size,
+                              int nr_channels, const idg_metadata_t *metadata,
+                              const idg_uvw_t *uvw, const float *wavenumbers,
+                              const float *weights, uint64_t *density,
+                              void *stream) {
+  WeightCall call;
+  if (int rc = parse_weight(params, nr_subgrids, subgrid_size, nr_channels,
+                            &call))
+    return rc;
+  if (nr_subgrids == 0) return IDG_OK;
+  if (!metadata || !uvw || !wavenumbers || !weights || !density)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_weight_density_launch: null buffer");
+  return from_hip(idg_mi355x::launch_weight_density(
+                      call.g, nr_subgrids, subgrid_size, nr_channels, metadata,
+                      uvw, wavenumbers, weights, density,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_weight_density_launch");
+}
+
+int idg_weight_scheme(const idg_weight_params_t *params,
+                      const uint64_t *density, float ab[2]) {
+  namespace wt = idg_mi355x::weight;
+  WeightCall call;
+  if (int rc = parse_weight(params, 0, 1, 1, &call)) return rc;
+  if (!density || !ab)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_scheme: null buffer");
+  if (int rc = check_density_cells(call.g, density)) return rc;
+  double sum_d = 0.0, sum_d2 = 0.0;
+  if (call.scheme == wt::kBriggs) {
+    const int G = call.g.grid_size;
+    for (int y = 0; y < G; ++y)
+      for (int x = 0; x < G; ++x) {
+        const double D = wt::density_of(wt::count_at(call.g, density, x, y),
+                                        call.g.quantum_log2);
+        sum_d += D;
+        sum_d2 += D * D;
+      }
+  }
+  wt::scheme_ab(call.scheme, call.briggs_scale, sum_d, sum_d2, &ab[0], &ab[1]);
+  return IDG_OK;
+}
+
+int idg_weight_scheme_launch(const idg_weight_params_t *params,
+                             const uint64_t *density, float ab[2],
+                             void *stream) {
+  WeightCall call;
+  if (int rc = parse_weight(params, 0, 1, 1, &call)) return rc;
+  if (!density || !ab)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_weight_scheme_launch: null buffer");
+  return from_hip(idg_mi355x::launch_weight_scheme(
+                      call.g, call.scheme, call.briggs_scale, density, ab,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_weight_scheme_launch");
+}
+
+int idg_weight_apply(const idg_weight_params_t *params, int nr_subgrids,
+                     int nr_channels, const idg_metadata_t *metadata,
+                     const idg_uvw_t *uvw, size_t uvw_rows,
+                     const float *wavenumbers, const float *weights,
+                     const uint64_t *density, const float ab[2],
+                     const idg_cfloat_t *visibilities, float *imaging_weights,
+                     idg_cfloat_t *out, double *sum_weights) {
+  namespace wt = idg_mi355x::weight;
+  WeightCall call;
+  if (int rc = parse_weight(params, nr_subgrids, 1, nr_channels, &call))
+    return rc;
+  if (!sum_weights)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_apply: null buffer");
+  if (nr_subgrids == 0) {
+    *sum_weights = 0.0;
+    return IDG_OK;
+  }
+  if (!metadata || !uvw || !wavenumbers || !weights || !density || !ab ||
+      !imaging_weights || !out)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_apply: null buffer");
+  if (int rc = check_weight_rows(nr_subgrids, uvw_rows, metadata)) return rc;
+  if (int rc = check_density_cells(call.g, density)) return rc;
+  const size_t C = nr_channels;
+  const float a = ab[0], b = ab[1];
+  double sum = 0.0;
+  for (int s = 0; s < nr_subgrids; ++s) {
+    const size_t row0 = static_cast<size_t>(weight_row0(metadata, s));
+    for (int t = 0; t < metadata[s].nr_timesteps; ++t) {
+      const size_t row = row0 + t;
+      for (size_t c = 0; c < C; ++c) {
+        const size_t at = row * C + c;
+        const float w = weights[at];
+        int x, y;
+        const bool live = wt::sample(call.g, uvw[row].u, uvw[row].v,
+                                     wavenumbers[c], w, &x, &y) != 0;
+        const float f =
+            live ? wt::imaging_weight(
+                       w, a, b,
+                       wt::density_of(wt::count_at(call.g, density, x, y),
+                                      call.g.quantum_log2))
+                 : 0.0f;
+        idg_cfloat_t *o = out + at * 4;
+        if (visibilities == nullptr) {
+          o[0] = o[3] = idg_cfloat_t{f, 0.0f};
+          o[1] = o[2] = idg_cfloat_t{0.0f, 0.0f};
+        } else if (live) {
+          const idg_cfloat_t *v = visibilities + at * 4;
+          for (int p = 0; p < 4; ++p)
+            o[p] = idg_cfloat_t{f * v[p].re, f * v[p].im};
+        } else {
+          for (int p = 0; p < 4; ++p) o[p] = idg_cfloat_t{0.0f, 0.0f};
+        }
+        imaging_weights[at] = f;
+        sum += f;
+      }
+    }
+  }
+  *sum_weights = sum;
+  return IDG_OK;
+}
+
+int idg_weight_apply_launch(const idg_weight_params_t *params, int nr_subgrids,
+                            int nr_channels, const idg_metadata_t *metadata,
+                            const idg_uvw_t *uvw, const float *wavenumbers,
+                            const float *weights, const uint64_t *density,
+                            const float ab[2],
+                            const idg_cfloat_t *visibilities,
+                            float *imaging_weights, idg_cfloat_t *out,
+                            double *sum_weights, void *stream) {
+  WeightCall call;
+  if (int rc = parse_weight(params, nr_subgrids, 1, nr_channels, &call))
+    return rc;
+  if (!sum_weights ||
+      (nr_subgrids > 0 && (!metadata || !uvw || !wavenumbers || !weights ||
+                           !density || !ab || !imaging_weights || !out)))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_weight_apply_launch: null buffer");
+  if ((reinterpret_cast<uintptr_t>(visibilities) |
+       reinterpret_cast<uintptr_t>(out)) % 16 != 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_weight_apply_launch: visibilities and out must be "
+                "16-byte aligned");
+  return from_hip(idg_mi355x::launch_weight_apply(
+                      call.g, nr_subgrids, nr_channels, metadata, uvw,
+                      wavenumbers, weights, density, ab, visibilities,
+                      imaging_weights, out, sum_weights,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_weight_apply_launch");
 }
 
 double idg_p_run_gridder(void) {

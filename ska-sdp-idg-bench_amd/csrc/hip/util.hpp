@@ -186,7 +186,8 @@ hipError_t launch_parts(const KernelChoice &k, int nr_subgrids, void **args13,
 // host thread holds the slot, ptr is a private stream-ordered allocation
 // (never clean) freed after the sequence.
 constexpr int kWorkspaceQueue = 0, kWorkspaceHomeSort = 1,
-              kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3, kWorkspacePlan = 4;
+              kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3, kWorkspacePlan = 4,
+              kWorkspaceWeight = 5;
 // Not copyable: a copy would release the slot twice.
 struct WorkspaceLease {
   void *ptr = nullptr;
@@ -318,6 +319,38 @@ hipError_t launch_plan(const plan::Geometry &geometry, float image_size,
                        const void *d_uvw, const float *d_wavenumbers,
                        void *d_metadata, int capacity, void *d_counts,
                        hipStream_t stream);
+
+// Imaging weights on the device (kernels/weight_mi355x.hip.cpp; DESIGN.md
+// §14), bit for bit the host entries of common/weight.hpp's arithmetic.
+// launch_weight_density adds the covered samples' quantised weights onto
+// d_density ([G][G] uint64; integer atomics, so the bits do not depend on any
+// order); launch_weight_scheme writes (a, b) of a scheme (weight::kNatural /
+// kUniform / kBriggs; briggs_scale = (5 * 10^-robust)^2) to d_ab from fixed-
+// order sums over the cells; launch_weight_apply writes the imaging weights,
+// the weighted visibilities (d_visibilities null: (f, 0, 0, f); d_out may be
+// d_visibilities; both 16-byte aligned) and *d_sum_weights for every covered
+// sample.  The partials of the two sums live on a kWorkspaceWeight lease;
+// nothing is read back.
+namespace weight {
+struct Geometry;
+}
+hipError_t launch_weight_density(const weight::Geometry &geometry,
+                                 int nr_subgrids, int subgrid_size,
+                                 int nr_channels, const void *d_metadata,
+                                 const void *d_uvw, const float *d_wavenumbers,
+                                 const float *d_weights, void *d_density,
+                                 hipStream_t stream);
+hipError_t launch_weight_scheme(const weight::Geometry &geometry, int scheme,
+                                double briggs_scale, const void *d_density,
+                                float *d_ab, hipStream_t stream);
+hipError_t launch_weight_apply(const weight::Geometry &geometry,
+                               int nr_subgrids, int nr_channels,
+                               const void *d_metadata, const void *d_uvw,
+                               const float *d_wavenumbers,
+                               const float *d_weights, const void *d_density,
+                               const float *d_ab, const void *d_visibilities,
+                               float *d_imaging_weights, void *d_out,
+                               double *d_sum_weights, hipStream_t stream);
 
 // Returns an empty string if every subgrid's time range, stations and A-term
 // slot lie inside the buffers, else a description of the first violation.

@@ -17,8 +17,10 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   splitter_fft_launch, splitter_launch, subgrid_fft_launch,
                   validate_metadata,
                   grid_fft_launch, grid_to_image, image_to_grid, invert,
-                  predict, taper_to_image)
-from ._lib import LIB_PATH, OptionsStruct, PlanParamsStruct
+                  predict, taper_to_image,
+                  psf, weigh, weight_apply, weight_density, weight_scheme)
+from ._lib import (LIB_PATH, OptionsStruct, PlanParamsStruct,
+                   WeightParamsStruct)
 from . import shard
 
 __all__ = [
@@ -34,4 +36,6 @@ __all__ = [
     "auto_selected", "plan", "plan_launch", "PlanParamsStruct",
     "grid_fft_launch", "grid_to_image", "image_to_grid", "invert", "predict",
     "taper_to_image",
+    "psf", "weigh", "weight_apply", "weight_density", "weight_scheme",
+    "WeightParamsStruct",
 ]

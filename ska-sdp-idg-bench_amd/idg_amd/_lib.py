@@ -73,6 +73,15 @@ SIGNATURES = {
     "idg_grid_to_image_launch": (_I, [_I, _I, _F, _F, _P, _P, _P, _P]),
     "idg_image_to_grid_launch": (_I, [_I, _I, _F, _F, _P, _P, _P, _P]),
     "idg_taper_to_image": (_I, [_I, _I, _P, _P]),
+    "idg_weight_density": (_I, [_P, _I, _I, _I, _P, _P, _Z, _P, _P, _P]),
+    "idg_weight_density_launch": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P,
+                                       _P]),
+    "idg_weight_scheme": (_I, [_P, _P, _P]),
+    "idg_weight_scheme_launch": (_I, [_P, _P, _P, _P]),
+    "idg_weight_apply": (_I, [_P, _I, _I, _P, _P, _Z, _P, _P, _P, _P, _P, _P,
+                              _P, _P]),
+    "idg_weight_apply_launch": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P]),
 }
 
 
@@ -94,6 +103,17 @@ class PlanParamsStruct(ctypes.Structure):
                 ("kernel_size", ctypes.c_int32),
                 ("max_nr_timesteps_per_subgrid", ctypes.c_int32),
                 ("nr_timesteps_per_aterm", ctypes.c_int32)]
+
+
+class WeightParamsStruct(ctypes.Structure):
+    """idg_weight_params_t (include/idg_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32),
+                ("grid_size", ctypes.c_int32),
+                ("image_size", ctypes.c_float),
+                ("quantum_log2", ctypes.c_int32),
+                ("hermitian", ctypes.c_int32),
+                ("scheme", ctypes.c_int32),
+                ("robust", ctypes.c_float)]
 
 
 def _load():

@@ -17,7 +17,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import OptionsStruct, PlanParamsStruct, lib
+from ._lib import OptionsStruct, PlanParamsStruct, WeightParamsStruct, lib
 
 IMAGE_SIZE = 0.01   # app/common/parameters.hpp:4
 W_STEP = 0.0        # app/common/parameters.hpp:5
@@ -758,14 +758,18 @@ def invert(nr_subgrids, grid_size, subgrid_size, image_size,
            w_step_in_lambda, nr_channels, nr_stations, uvw, wavenumbers,
            visibilities, spheroidal, aterms, metadata, grid=None,
            nr_w_layers=1, subgrids=None, stream=None, options=None,
-           correction=None, image=None):
+           correction=None, image=None, sum_weights=None):
     """Visibilities -> dirty image [4, G, G, 2] float32: grid_onto, then
     grid_to_image.  The exact adjoint of predict; not divided by the number
     of visibilities (one unit visibility with identity A-terms gives modulus
     ~1 everywhere).  grid: None (a zeroed grid is made) or a [W, 4, G, G, 2]
     grid to accumulate onto; it is destroyed.  correction: float32 [G, G]
     (1 / taper_to_image) or None; the 1 / S^2 that undoes the gridding FFT's
-    normalisation is folded into it here."""
+    normalisation is folded into it here.  sum_weights: None, or the float64
+    device tensor weight_apply / weigh wrote (the sum of the imaging weights):
+    the image is divided by it, folded into the same correction on the device
+    (nothing is read back), so that a unit point source weighted by weigh()
+    images to 1."""
     import torch
     if correction is not None and correction.numel() != grid_size * grid_size:
         raise ValueError(f"correction must be [{grid_size}][{grid_size}] "
@@ -784,6 +788,12 @@ def invert(nr_subgrids, grid_size, subgrid_size, image_size,
                                 dtype=torch.float32, device=dev)
         else:
             scaled = (correction.to(torch.float32) * inv).contiguous()
+        if sum_weights is not None:
+            if sum_weights.numel() != 1 or sum_weights.dtype != torch.float64:
+                raise ValueError("sum_weights must be one float64 on the "
+                                 "device")
+            scaled = (scaled.to(torch.float64) / sum_weights.reshape(())
+                      ).to(torch.float32).contiguous()
         grid_onto(nr_subgrids, grid_size, subgrid_size, image_size,
                   w_step_in_lambda, nr_channels, nr_stations, uvw,
                   wavenumbers, visibilities, spheroidal, aterms, metadata,
@@ -809,6 +819,259 @@ def predict(nr_subgrids, grid_size, subgrid_size, image_size,
                     wavenumbers, visibilities, spheroidal, aterms, metadata,
                     grid, nr_w_layers, subgrids, stream, options)
     return grid
+
+
+# ---------------------------------------------------------------------------
+# Imaging weights (idg_weight_*; not in the reference): the uv
+# sampling density of the samples the gridder will grid, the (a, b) of
+# natural / uniform / Briggs weighting, f = w / (a + b D), the weighted
+# visibilities and the sum of f.  Each mirror takes numpy arrays (the host
+# entry, no device needed) or torch CUDA tensors (the _launch entry,
+# asynchronous, nothing read back) and produces the same bytes.
+#   weigh: density -> scheme -> apply      psf: apply(None) -> invert
+# ---------------------------------------------------------------------------
+SCHEMES = {"natural": 0, "uniform": 1, "briggs": 2}
+QUANTUM_LOG2 = -20      # weights are counted in units of 2^-20
+
+
+def _weight_params(grid_size, image_size, quantum_log2, hermitian,
+                   scheme="natural", robust=0.0):
+    p = WeightParamsStruct()
+    p.struct_size = ctypes.sizeof(WeightParamsStruct)
+    p.grid_size = grid_size
+    p.image_size = image_size
+    p.quantum_log2 = quantum_log2
+    p.hermitian = 1 if hermitian else 0
+    p.scheme = _enum(scheme, SCHEMES, "scheme")
+    p.robust = robust
+    return p, ctypes.cast(ctypes.pointer(p), ctypes.c_void_p)
+
+
+def _weight_inputs(uvw, wavenumbers, weights, metadata):
+    """(host?, rows, C, nr_subgrids, pointers of uvw / wavenumbers / weights /
+    metadata, keep-alive) of a density or apply call, shapes checked."""
+    host = isinstance(uvw, np.ndarray)
+    if host:
+        md = as_metadata(metadata)
+        rows, C, ns = uvw.size // 3, wavenumbers.size, md.size
+        if uvw.size % 3:
+            raise ValueError("uvw must hold whole (u, v, w) triplets")
+        if weights.size != rows * C:
+            raise ValueError(f"weights must be [{rows}][{C}] float32")
+        ptrs = (_np_ptr(uvw, np.float32, "uvw"),
+                _np_ptr(wavenumbers, np.float32, "wavenumbers"),
+                _np_ptr(weights, np.float32, "weights"),
+                _np_ptr(md, METADATA_DTYPE, "metadata"))
+        return host, rows, C, ns, ptrs, md
+    import torch
+    rows, C = uvw.numel() // 3, wavenumbers.numel()
+    if uvw.numel() % 3:
+        raise ValueError("uvw must hold whole (u, v, w) triplets")
+    if weights.numel() != rows * C:
+        raise ValueError(f"weights must be [{rows}][{C}] float32")
+    nbytes = metadata.numel() * metadata.element_size()
+    if nbytes % 36:
+        raise ValueError("metadata must hold whole 36-byte records")
+    ptrs = (_dev_ptr(uvw, "uvw", torch.float32),
+            _dev_ptr(wavenumbers, "wavenumbers", torch.float32),
+            _dev_ptr(weights, "weights", torch.float32),
+            _dev_ptr(metadata, "metadata") if nbytes else None)
+    return host, rows, C, nbytes // 36, ptrs, None
+
+
+def _density_buffer(host, grid_size, density, device=None):
+    G = grid_size
+    if host:
+        if density is None:
+            return np.zeros((G, G), np.uint64)
+        if density.size != G * G:
+            raise ValueError(f"density must be [{G}][{G}] uint64")
+        return density
+    import torch
+    if density is None:
+        return torch.zeros((G, G), dtype=torch.int64, device=device)
+    if density.numel() != G * G or density.dtype != torch.int64:
+        raise ValueError(f"density must be [{G}][{G}] int64 (the bits of the "
+                         "library's uint64)")
+    return density
+
+
+def weight_density(grid_size, subgrid_size, image_size, uvw, wavenumbers,
+                   weights, metadata, density=None, quantum_log2=QUANTUM_LOG2,
+                   stream=None):
+    """density[Y][X] += the sum over the samples the metadata covers of their
+    weights in units of 2^quantum_log2, at the nearest uv cell of each sample
+    (idg_weight_density / idg_weight_density_launch).  weights: float32
+    [rows, C], 0 = flagged.  density: uint64 [G, G] (numpy) / int64 [G, G]
+    (torch: the same bits) to accumulate onto, or None for a zeroed one.
+    Keep every cell's sum below 2^62.  Exact: the same bits in any order, on
+    the host and on the device.  Returns the density."""
+    host, rows, C, ns, ptrs, keep = _weight_inputs(uvw, wavenumbers, weights,
+                                                   metadata)
+    # (a fresh device density is zeroed on `stream`, ahead of the launch)
+    with contextlib.nullcontext() if host else _on_stream(stream):
+        density = _density_buffer(host, grid_size, density,
+                                  None if host else uvw.device)
+    p, pp = _weight_params(grid_size, image_size, quantum_log2, True)
+    if host:
+        _check(lib.idg_weight_density(
+            pp, ns, subgrid_size, C, ptrs[3], ptrs[0], rows, ptrs[1], ptrs[2],
+            _np_ptr(density, np.uint64, "density", True)), "weight_density")
+    else:
+        _check(lib.idg_weight_density_launch(
+            pp, ns, subgrid_size, C, ptrs[3], ptrs[0], ptrs[1], ptrs[2],
+            _dev_ptr(density, "density"), _stream_handle(stream)),
+            "weight_density")
+    return density
+
+
+def weight_scheme(grid_size, density, scheme="natural", robust=0.0,
+                  quantum_log2=QUANTUM_LOG2, hermitian=True, ab=None,
+                  stream=None):
+    """(a, b) of f = w / (a + b D) for "natural" (1, 0), "uniform" (0, 1) or
+    "briggs" (1, (5 10^-robust)^2 sum D / sum D^2 over all cells) at this
+    density (idg_weight_scheme / idg_weight_scheme_launch): float32 [2], a
+    numpy array for a numpy density, a device tensor (nothing read back) for a
+    device one."""
+    p, pp = _weight_params(grid_size, 0.0, quantum_log2, hermitian, scheme,
+                           float(robust))
+    if isinstance(density, np.ndarray):
+        if density.size != grid_size * grid_size:
+            raise ValueError("density must be [G][G] uint64")
+        if ab is None:
+            ab = np.zeros(2, np.float32)
+        _check(lib.idg_weight_scheme(
+            pp, _np_ptr(density, np.uint64, "density"),
+            _np_ptr(ab, np.float32, "ab", True)), "weight_scheme")
+        return ab
+    import torch
+    density = _density_buffer(False, grid_size, density)
+    if ab is None:
+        with _on_stream(stream):
+            ab = torch.zeros(2, dtype=torch.float32, device=density.device)
+    _check(lib.idg_weight_scheme_launch(
+        pp, _dev_ptr(density, "density"), _dev_ptr(ab, "ab", torch.float32),
+        _stream_handle(stream)), "weight_scheme")
+    return ab
+
+
+def weight_apply(grid_size, image_size, uvw, wavenumbers, weights, metadata,
+                 density, ab, visibilities=None, imaging_weights=None,
+                 out=None, sum_weights=None, quantum_log2=QUANTUM_LOG2,
+                 hermitian=True, stream=None):
+    """For every sample the metadata covers: imaging_weights = f =
+    w / (a + b D), out = f * visibilities ((f, 0, 0, f) with visibilities
+    None, the PSF's input; literal zeros for a flagged sample), sum_weights =
+    sum f in float64 (idg_weight_apply / idg_weight_apply_launch).  out may
+    be visibilities.  Rows no subgrid covers are left as they were; buffers
+    made here start as zeros.  Returns (imaging_weights [rows, C], out
+    [rows, C, 4, 2], sum_weights [1] float64)."""
+    host, rows, C, ns, ptrs, keep = _weight_inputs(uvw, wavenumbers, weights,
+                                                   metadata)
+    p, pp = _weight_params(grid_size, image_size, quantum_log2, hermitian)
+    if visibilities is not None and (
+            (visibilities.size if host else visibilities.numel())
+            != rows * C * 8):
+        raise ValueError(f"visibilities must be [{rows}][{C}][4] complex")
+    if host:
+        if imaging_weights is None:
+            imaging_weights = np.zeros((rows, C), np.float32)
+        if out is None:
+            out = np.zeros((rows, C, 4, 2), np.float32)
+        if sum_weights is None:
+            sum_weights = np.zeros(1, np.float64)
+        if imaging_weights.size != rows * C or out.size != rows * C * 8:
+            raise ValueError("imaging_weights must be [rows][C], out "
+                             "[rows][C][4] complex")
+        _check(lib.idg_weight_apply(
+            pp, ns, C, ptrs[3], ptrs[0], rows, ptrs[1], ptrs[2],
+            _np_ptr(density, np.uint64, "density"),
+            _np_ptr(ab, np.float32, "ab"),
+            None if visibilities is None else _np_ptr(
+                visibilities, np.float32, "visibilities"),
+            _np_ptr(imaging_weights, np.float32, "imaging_weights", True),
+            _np_ptr(out, np.float32, "out", True),
+            _np_ptr(sum_weights, np.float64, "sum_weights", True)),
+            "weight_apply")
+        return imaging_weights, out, sum_weights
+    import torch
+    dev = uvw.device
+    density = _density_buffer(False, grid_size, density)
+    with _on_stream(stream):
+        if imaging_weights is None:
+            imaging_weights = torch.zeros((rows, C), dtype=torch.float32,
+                                          device=dev)
+        if out is None:
+            out = torch.zeros((rows, C, 4, 2), dtype=torch.float32,
+                              device=dev)
+        if sum_weights is None:
+            sum_weights = torch.zeros(1, dtype=torch.float64, device=dev)
+    if imaging_weights.numel() != rows * C or out.numel() != rows * C * 8:
+        raise ValueError("imaging_weights must be [rows][C], out "
+                         "[rows][C][4] complex")
+    _check(lib.idg_weight_apply_launch(
+        pp, ns, C, ptrs[3], ptrs[0], ptrs[1], ptrs[2],
+        _dev_ptr(density, "density"), _dev_ptr(ab, "ab", torch.float32),
+        None if visibilities is None else _dev_ptr(
+            visibilities, "visibilities", torch.float32),
+        _dev_ptr(imaging_weights, "imaging_weights", torch.float32),
+        _dev_ptr(out, "out", torch.float32),
+        _dev_ptr(sum_weights, "sum_weights", torch.float64),
+        _stream_handle(stream)), "weight_apply")
+    return imaging_weights, out, sum_weights
+
+
+def weigh(grid_size, subgrid_size, image_size, uvw, wavenumbers, weights,
+          metadata, visibilities=None, scheme="natural", robust=0.0,
+          density=None, out=None, quantum_log2=QUANTUM_LOG2, hermitian=True,
+          stream=None):
+    """weight_density -> weight_scheme -> weight_apply in one go, on the
+    device with nothing read back between the steps (or on the host, for
+    numpy inputs).  density: None (this batch's own) or one to accumulate
+    onto first.  Returns (imaging_weights, weighted visibilities,
+    sum_weights, density, ab)."""
+    with (contextlib.nullcontext() if isinstance(uvw, np.ndarray)
+          else _on_stream(stream)):
+        density = weight_density(grid_size, subgrid_size, image_size, uvw,
+                                 wavenumbers, weights, metadata, density,
+                                 quantum_log2, stream)
+        ab = weight_scheme(grid_size, density, scheme, robust, quantum_log2,
+                           hermitian, None, stream)
+        iw, out, total = weight_apply(
+            grid_size, image_size, uvw, wavenumbers, weights, metadata,
+            density, ab, visibilities, None, out, None, quantum_log2,
+            hermitian, stream)
+    return iw, out, total, density, ab
+
+
+def psf(grid_size, subgrid_size, image_size, w_step_in_lambda, nr_stations,
+        uvw, wavenumbers, weights, spheroidal, metadata, scheme="natural",
+        robust=0.0, density=None, nr_w_layers=1, aterm_slots=1,
+        correction=None, quantum_log2=QUANTUM_LOG2, hermitian=True,
+        stream=None, options=None):
+    """The point spread function [4, G, G, 2] float32 of these samples under
+    a weighting scheme, on the device: weigh() with no visibilities (each
+    covered sample becomes (f, 0, 0, f)), then invert() with identity
+    A-terms and sum_weights, so the centre pixel of xx and yy is 1 (as far as
+    `correction` undoes the taper there).  aterm_slots: the A-term slots the
+    metadata refers to.  density: as for weigh()."""
+    import torch
+    S, C = subgrid_size, wavenumbers.numel()
+    ns = metadata.numel() * metadata.element_size() // 36
+    with _on_stream(stream):
+        iw, vis, total, density, ab = weigh(
+            grid_size, S, image_size, uvw, wavenumbers, weights, metadata,
+            None, scheme, robust, density, None, quantum_log2, hermitian,
+            stream)
+        aterms = torch.zeros((aterm_slots, nr_stations, S, S, 4, 2),
+                             dtype=torch.float32, device=uvw.device)
+        aterms[..., 0, 0] = 1.0
+        aterms[..., 3, 0] = 1.0
+        return invert(ns, grid_size, S, image_size, w_step_in_lambda, C,
+                      nr_stations, uvw, wavenumbers, vis, spheroidal, aterms,
+                      metadata, nr_w_layers=nr_w_layers, stream=stream,
+                      options=options, correction=correction,
+                      sum_weights=total)
 
 
 # ---------------------------------------------------------------------------
