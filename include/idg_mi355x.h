@@ -633,6 +633,88 @@ int idg_weight_apply_launch(const idg_weight_params_t *params, int nr_subgrids,
                             float *imaging_weights, idg_cfloat_t *out,
                             double *sum_weights, void *stream);
 
+/* ---- Hogbom CLEAN minor cycle ----------------------------------
+ * Dirty image -> model, on one real plane: find the peak, take gain * peak as
+ * a component, subtract component * psf around it, again.  No reference
+ * counterpart; idg_clean (host pointers, no device needed) and
+ * idg_clean_launch (device pointers, asynchronous on `stream`, nothing read
+ * back, no synchronisation, scratch from the workspace cache) produce the
+ * same bytes in every output.
+ *
+ * residual: float32 [G][G], updated in place.  psf: float32 [Gp][Gp], centre
+ * at (Gp / 2, Gp / 2) (integer division), 1 <= Gp <= G <= 16384; it is used as
+ * it is, not divided by its centre.  mask: uint8 [G][G] or NULL; a pixel is
+ * searchable iff its byte is non-zero (NULL: all are); the mask limits the
+ * search only, never the subtraction.  model: float32 [G][G], accumulated
+ * onto (the caller zeroes it).  components: [max_components] records.  state:
+ * input and output; the caller zeroes it before the first call, and any later
+ * call with the same buffers continues from it: k calls of n iterations give
+ * exactly the bytes of one call of k * n.
+ *
+ * Peak: among the searchable pixels whose value is not NaN the largest |s|,
+ * ties (+v against -v too) to the lowest linear index y * G + x; v is the
+ * signed value there.  One iteration, in this order:
+ *   1. reason != 0: nothing.
+ *   2. no peak: reason = IDG_CLEAN_NO_PEAK, stop.
+ *   3. started == 0: level = fmaxf(threshold, cycle_fraction * |v|) (one
+ *      rounded multiply), started = 1.
+ *   4. !(|v| > level): reason = IDG_CLEAN_BELOW_LEVEL, stop.
+ *   5. n_components == max_components: reason = IDG_CLEAN_COMPONENTS_FULL, stop.
+ *   6. c = gain * v (one rounded multiply); components[n_components++] =
+ *      {py, px, c}; model[py][px] += c (one add).
+ *   7. every (y, x) with dy = y - py + Gp / 2 and dx = x - px + Gp / 2 inside
+ *      [0, Gp): residual[y][x] = fmaf(-c, psf[dy][dx], residual[y][x]).
+ * After the last iteration state.peak = |s| at the peak of the residual as it
+ * stands (0 if none) and state.peak_index its linear index (-1 if none);
+ * reason stays 0 when the call only ran out of iterations.  nr_iterations = 0
+ * refreshes those two fields and nothing else.
+ *
+ * IDG_E_INVALID_ARGUMENT (every buffer left as it was): a bad struct_size
+ * (the rules of idg_options_t), sizes out of range, gain / threshold /
+ * cycle_fraction not finite, threshold or cycle_fraction negative,
+ * nr_iterations < 0 or max_components < 0, a NULL buffer other than mask,
+ * and (host form, which can read it) a state with n_components outside
+ * [0, max_components]; on such a state the _launch form runs no iteration. */
+#define IDG_CLEAN_RUNNING 0
+#define IDG_CLEAN_BELOW_LEVEL 1
+#define IDG_CLEAN_NO_PEAK 2
+#define IDG_CLEAN_COMPONENTS_FULL 3
+
+typedef struct idg_clean_params_t {
+  uint32_t struct_size; /* sizeof(idg_clean_params_t)                        */
+  int32_t grid_size;    /* G                                                 */
+  int32_t psf_size;     /* Gp                                                */
+  int32_t max_components;
+  int32_t nr_iterations;
+  float gain;
+  float threshold;
+  float cycle_fraction;
+} idg_clean_params_t;
+
+typedef struct idg_clean_component_t {
+  int32_t y, x;
+  float value;
+} idg_clean_component_t;
+
+typedef struct idg_clean_state_t {
+  int32_t n_components;
+  int32_t reason;     /* IDG_CLEAN_*                                         */
+  int32_t started;    /* != 0: level is set                                  */
+  int32_t peak_index; /* y * G + x of the residual's peak, -1: none          */
+  float level;
+  float peak;
+} idg_clean_state_t;
+
+int idg_clean(const idg_clean_params_t *params, float *residual,
+              const float *psf, const uint8_t *mask, float *model,
+              idg_clean_component_t *components, idg_clean_state_t *state);
+/* One launch per iteration plus two: a caller who wants to stop early reads
+ * state->reason between calls of a few iterations each. */
+int idg_clean_launch(const idg_clean_params_t *params, float *residual,
+                     const float *psf, const uint8_t *mask, float *model,
+                     idg_clean_component_t *components,
+                     idg_clean_state_t *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

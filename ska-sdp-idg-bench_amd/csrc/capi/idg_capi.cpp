@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "common/clean.hpp"
 #include "common/plan.hpp"
 #include "common/weight.hpp"
 #include "hip/util.hpp"
@@ -268,6 +269,74 @@ int check_density_cells(const idg_mi355x::weight::Geometry &g,
                   "weight: density cell " + std::to_string(i) +
                       " is at or above 2^62");
   return IDG_OK;
+}
+
+// idg_clean_params_t (struct_size rules of idg_options_t) -> clean::Params.
+int parse_clean(const idg_clean_params_t *params,
+                idg_mi355x::clean::Params *out) {
+  if (params == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_clean_params_t: null");
+  const uint32_t size = params->struct_size;
+  if (size < sizeof(uint32_t) || size % 4 != 0 || size > (1u << 16))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_clean_params_t: struct_size " + std::to_string(size) +
+                    " (set it to sizeof(idg_clean_params_t))");
+  idg_clean_params_t v;
+  std::memset(&v, 0, sizeof v);
+  std::memcpy(&v, params, std::min<size_t>(size, sizeof v));
+  const unsigned char *raw = reinterpret_cast<const unsigned char *>(params);
+  for (size_t i = sizeof v; i < size; ++i)
+    if (raw[i] != 0)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "idg_clean_params_t: struct_size " + std::to_string(size) +
+                      " with a field set that this library (struct_size " +
+                      std::to_string(sizeof v) + ") does not know");
+  if (v.psf_size < 1 || v.grid_size < v.psf_size ||
+      v.grid_size > idg_mi355x::clean::kMaxGridSize)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clean: 1 <= psf_size <= grid_size <= 16384 required");
+  if (!std::isfinite(v.gain) || !std::isfinite(v.threshold) ||
+      !std::isfinite(v.cycle_fraction) || v.threshold < 0.0f ||
+      v.cycle_fraction < 0.0f)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clean: gain, threshold and cycle_fraction must be finite, "
+                "threshold and cycle_fraction not negative");
+  if (v.nr_iterations < 0 || v.max_components < 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clean: nr_iterations >= 0 and max_components >= 0 required");
+  out->grid_size = v.grid_size;
+  out->psf_size = v.psf_size;
+  out->max_components = v.max_components;
+  out->nr_iterations = v.nr_iterations;
+  out->gain = v.gain;
+  out->threshold = v.threshold;
+  out->cycle_fraction = v.cycle_fraction;
+  return IDG_OK;
+}
+static_assert(IDG_CLEAN_RUNNING == idg_mi355x::clean::kRunning &&
+                  IDG_CLEAN_BELOW_LEVEL == idg_mi355x::clean::kBelowLevel &&
+                  IDG_CLEAN_NO_PEAK == idg_mi355x::clean::kNoPeak &&
+                  IDG_CLEAN_COMPONENTS_FULL ==
+                      idg_mi355x::clean::kComponentsFull &&
+                  sizeof(idg_clean_component_t) ==
+                      sizeof(idg_mi355x::clean::Component) &&
+                  sizeof(idg_clean_component_t) == 12 &&
+                  sizeof(idg_clean_state_t) ==
+                      sizeof(idg_mi355x::clean::State) &&
+                  sizeof(idg_clean_state_t) == 24,
+              "idg_clean_* records are clean:: records");
+
+// The key of the residual's peak (clean::key_of; 0: none), row-major.
+uint64_t clean_peak(const idg_mi355x::clean::Params &p, const float *residual,
+                    const uint8_t *mask) {
+  const size_t cells = static_cast<size_t>(p.grid_size) * p.grid_size;
+  uint64_t best = 0;
+  for (size_t i = 0; i < cells; ++i) {
+    const uint64_t key = idg_mi355x::clean::key_of(
+        residual[i], static_cast<uint32_t>(i), mask == nullptr || mask[i] != 0);
+    if (key > best) best = key;
+  }
+  return best;
 }
 
 int check_geometry(const idg_mi355x::Problem &p) {
@@ -1022,6 +1091,60 @@ int idg_weight_apply_launch(const idg_weight_params_t *params, int nr_subgrids,
                       imaging_weights, out, sum_weights,
                       static_cast<hipStream_t>(stream)),
                   "idg_weight_apply_launch");
+}
+
+int idg_clean(const idg_clean_params_t *params, float *residual,
+              const float *psf, const uint8_t *mask, float *model,
+              idg_clean_component_t *components, idg_clean_state_t *state) {
+  namespace cl = idg_mi355x::clean;
+  cl::Params p;
+  if (int rc = parse_clean(params, &p)) return rc;
+  if (!residual || !psf || !model || !components || !state)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_clean: null buffer");
+  cl::State s;
+  std::memcpy(&s, state, sizeof s);
+  if (!cl::state_ok(s, p))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_clean: state.n_components " +
+                    std::to_string(s.n_components) + " outside [0, " +
+                    std::to_string(p.max_components) + "]");
+  const size_t G = static_cast<size_t>(p.grid_size);
+  const size_t Gp = static_cast<size_t>(p.psf_size);
+  uint64_t key = 0;
+  for (int k = 0;; ++k) {
+    key = clean_peak(p, residual, mask);
+    if (k == p.nr_iterations) break;
+    float c = 0.0f;
+    const uint32_t index = key != 0 ? cl::index_of(key) : 0;
+    if (!cl::step(&s, p, key, key != 0 ? residual[index] : 0.0f, &c)) break;
+    const int py = static_cast<int>(index / G), px = static_cast<int>(index % G);
+    components[s.n_components - 1] = {py, px, c};
+    model[index] = model[index] + c;
+    const cl::Patch pt = cl::patch_of(p, py, px);
+    for (int y = pt.y0; y < pt.y1; ++y) {
+      float *row = residual + static_cast<size_t>(y) * G;
+      const float *prow = psf + static_cast<size_t>(y - pt.oy) * Gp;
+      for (int x = pt.x0; x < pt.x1; ++x)
+        row[x] = cl::subtract(c, prow[x - pt.ox], row[x]);
+    }
+  }
+  cl::set_peak(&s, key);
+  std::memcpy(state, &s, sizeof s);
+  return IDG_OK;
+}
+
+int idg_clean_launch(const idg_clean_params_t *params, float *residual,
+                     const float *psf, const uint8_t *mask, float *model,
+                     idg_clean_component_t *components,
+                     idg_clean_state_t *state, void *stream) {
+  idg_mi355x::clean::Params p;
+  if (int rc = parse_clean(params, &p)) return rc;
+  if (!residual || !psf || !model || !components || !state)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_clean_launch: null buffer");
+  return from_hip(idg_mi355x::launch_clean(p, residual, psf, mask, model,
+                                           components, state,
+                                           static_cast<hipStream_t>(stream)),
+                  "idg_clean_launch");
 }
 
 double idg_p_run_gridder(void) {

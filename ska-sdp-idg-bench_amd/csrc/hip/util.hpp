@@ -187,7 +187,7 @@ hipError_t launch_parts(const KernelChoice &k, int nr_subgrids, void **args13,
 // (never clean) freed after the sequence.
 constexpr int kWorkspaceQueue = 0, kWorkspaceHomeSort = 1,
               kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3, kWorkspacePlan = 4,
-              kWorkspaceWeight = 5;
+              kWorkspaceWeight = 5, kWorkspaceClean = 6;
 // Not copyable: a copy would release the slot twice.
 struct WorkspaceLease {
   void *ptr = nullptr;
@@ -351,6 +351,22 @@ hipError_t launch_weight_apply(const weight::Geometry &geometry,
                                const float *d_ab, const void *d_visibilities,
                                float *d_imaging_weights, void *d_out,
                                double *d_sum_weights, hipStream_t stream);
+
+// The Hogbom minor cycle on the device (kernels/clean_mi355x.hip.cpp; DESIGN.md
+// §15), bit for bit the host entry of common/clean.hpp's arithmetic: one
+// search launch, params.nr_iterations iteration launches (each subtracts one
+// component and searches for the next in the same pass) and one finish launch,
+// continuing from *d_state (clean::State) and leaving it there.  The tiles'
+// partials and the double-buffered state live on a kWorkspaceClean lease;
+// nothing is read back.  d_mask may be null; d_components: clean::Component
+// [params.max_components].
+namespace clean {
+struct Params;
+}
+hipError_t launch_clean(const clean::Params &params, float *d_residual,
+                        const float *d_psf, const uint8_t *d_mask,
+                        float *d_model, void *d_components, void *d_state,
+                        hipStream_t stream);
 
 // Returns an empty string if every subgrid's time range, stations and A-term
 // slot lie inside the buffers, else a description of the first violation.

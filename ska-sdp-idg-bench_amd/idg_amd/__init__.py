@@ -18,9 +18,11 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   validate_metadata,
                   grid_fft_launch, grid_to_image, image_to_grid, invert,
                   predict, taper_to_image,
-                  psf, weigh, weight_apply, weight_density, weight_scheme)
-from ._lib import (LIB_PATH, OptionsStruct, PlanParamsStruct,
-                   WeightParamsStruct)
+                  psf, weigh, weight_apply, weight_density, weight_scheme,
+                  CLEAN_REASONS, COMPONENT_DTYPE, STATE_DTYPE, clean,
+                  model_image, stokes_i)
+from ._lib import (LIB_PATH, CleanParamsStruct, OptionsStruct,
+                   PlanParamsStruct, WeightParamsStruct)
 from . import shard
 
 __all__ = [
@@ -38,4 +40,6 @@ __all__ = [
     "taper_to_image",
     "psf", "weigh", "weight_apply", "weight_density", "weight_scheme",
     "WeightParamsStruct",
+    "CLEAN_REASONS", "COMPONENT_DTYPE", "STATE_DTYPE", "clean", "model_image",
+    "stokes_i", "CleanParamsStruct",
 ]

@@ -82,6 +82,8 @@ SIGNATURES = {
                               _P, _P]),
     "idg_weight_apply_launch": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P]),
+    "idg_clean": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "idg_clean_launch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 
@@ -114,6 +116,18 @@ class WeightParamsStruct(ctypes.Structure):
                 ("hermitian", ctypes.c_int32),
                 ("scheme", ctypes.c_int32),
                 ("robust", ctypes.c_float)]
+
+
+class CleanParamsStruct(ctypes.Structure):
+    """idg_clean_params_t (include/idg_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32),
+                ("grid_size", ctypes.c_int32),
+                ("psf_size", ctypes.c_int32),
+                ("max_components", ctypes.c_int32),
+                ("nr_iterations", ctypes.c_int32),
+                ("gain", ctypes.c_float),
+                ("threshold", ctypes.c_float),
+                ("cycle_fraction", ctypes.c_float)]
 
 
 def _load():

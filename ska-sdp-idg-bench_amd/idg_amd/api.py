@@ -17,7 +17,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import OptionsStruct, PlanParamsStruct, WeightParamsStruct, lib
+from ._lib import (CleanParamsStruct, OptionsStruct, PlanParamsStruct,
+                   WeightParamsStruct, lib)
 
 IMAGE_SIZE = 0.01   # app/common/parameters.hpp:4
 W_STEP = 0.0        # app/common/parameters.hpp:5
@@ -1072,6 +1073,157 @@ def psf(grid_size, subgrid_size, image_size, w_step_in_lambda, nr_stations,
                       metadata, nr_w_layers=nr_w_layers, stream=stream,
                       options=options, correction=correction,
                       sum_weights=total)
+
+
+# ---------------------------------------------------------------------------
+# Hogbom CLEAN minor cycle (idg_clean / idg_clean_launch; DESIGN.md §15; not
+# in the reference): dirty image -> model on one real plane.  numpy arrays
+# take the host entry, torch CUDA tensors the _launch entry (asynchronous);
+# the same bytes either way.
+#   stokes_i(invert(...)), stokes_i(psf(...)) -> clean -> model_image ->
+#   predict
+# ---------------------------------------------------------------------------
+COMPONENT_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4"), ("value", "<f4")])
+STATE_DTYPE = np.dtype([("n_components", "<i4"), ("reason", "<i4"),
+                        ("started", "<i4"), ("peak_index", "<i4"),
+                        ("level", "<f4"), ("peak", "<f4")])
+assert COMPONENT_DTYPE.itemsize == 12 and STATE_DTYPE.itemsize == 24
+CLEAN_REASONS = {0: "running", 1: "below_level", 2: "no_peak",
+                 3: "components_full"}
+
+
+def stokes_i(image):
+    """[4, G, G, 2] (xx, xy, yx, yy as re / im pairs) -> [G, G] float32,
+    0.5 * (Re xx + Re yy): the plane clean() works on, of invert()'s image and
+    of psf()'s alike.  numpy or torch."""
+    if tuple(image.shape[:1]) != (4,) or tuple(image.shape[3:]) != (2,):
+        raise ValueError("image must be [4, G, G, 2]")
+    return 0.5 * (image[0, :, :, 0] + image[3, :, :, 0])
+
+
+def model_image(model):
+    """[G, G] -> [4, G, G, 2] float32 with xx = yy = model and the rest 0:
+    predict()'s input for an unpolarised model.  numpy or torch."""
+    if model.ndim != 2:
+        raise ValueError("model must be [G, G]")
+    if isinstance(model, np.ndarray):
+        out = np.zeros((4,) + model.shape + (2,), np.float32)
+    else:
+        import torch
+        out = torch.zeros((4,) + tuple(model.shape) + (2,),
+                          dtype=torch.float32, device=model.device)
+    out[0, :, :, 0] = model
+    out[3, :, :, 0] = model
+    return out
+
+
+def _clean_params(G, Gp, max_components, nr_iterations, gain, threshold,
+                  cycle_fraction):
+    p = CleanParamsStruct()
+    p.struct_size = ctypes.sizeof(CleanParamsStruct)
+    p.grid_size, p.psf_size = G, Gp
+    p.max_components, p.nr_iterations = max_components, nr_iterations
+    p.gain, p.threshold, p.cycle_fraction = gain, threshold, cycle_fraction
+    return p, ctypes.cast(ctypes.pointer(p), ctypes.c_void_p)
+
+
+def _square(a, name):
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError(f"{name} must be a square plane, got "
+                         f"{tuple(a.shape)}")
+    return a.shape[0]
+
+
+def clean(residual, psf, model=None, mask=None, gain=0.1, threshold=0.0,
+          cycle_fraction=0.0, max_components=1000, nr_iterations=None,
+          components=None, state=None, check_every=None, stream=None):
+    """Hogbom minor cycle (idg_clean / idg_clean_launch): up to nr_iterations
+    (None: max_components) times, take gain * the peak of `residual` as a
+    component, add it to `model` and subtract it times `psf` around the peak,
+    until the peak is no longer above max(threshold, cycle_fraction * the
+    first peak), no searchable pixel is left or `components` is full.
+    residual: float32 [G, G], updated in place.  psf: float32 [Gp, Gp], Gp <=
+    G, centre (Gp // 2, Gp // 2) of value 1 (psf() makes it so).  mask: uint8
+    or bool [G, G] or None: where 0, no peak is searched (the subtraction
+    goes everywhere).  model: float32 [G, G] to accumulate onto, or None for a
+    zeroed one.  components / state: None for fresh ones, or those of an
+    earlier call to continue it: k calls of n iterations give the bytes of one
+    call of k * n.  numpy: COMPONENT_DTYPE [max_components] and STATE_DTYPE
+    [1]; torch: the same bytes as int32 [max_components, 3] and int32 [6]
+    (view the float fields with .view(torch.float32)).  check_every = n
+    (device only): n iterations are enqueued at a time and the 4 bytes of
+    state.reason read back between the chunks, to stop enqueueing once it is
+    set; None reads nothing back.  Returns (residual, model, components,
+    state)."""
+    host = isinstance(residual, np.ndarray)
+    G, Gp = _square(residual, "residual"), _square(psf, "psf")
+    if nr_iterations is None:
+        nr_iterations = max_components
+    records = max(max_components, 1)     # (never a null pointer)
+    if host:
+        if model is None:
+            model = np.zeros((G, G), np.float32)
+        if components is None:
+            components = np.zeros(records, COMPONENT_DTYPE)
+        if state is None:
+            state = np.zeros(1, STATE_DTYPE)
+        if (model.shape != residual.shape or components.size < max_components
+                or state.size != 1
+                or (mask is not None and mask.shape != residual.shape)):
+            raise ValueError("model and mask must be [G][G], components "
+                             "[max_components], state [1]")
+        if mask is not None and mask.dtype == np.bool_:
+            mask = mask.view(np.uint8)
+        p, pp = _clean_params(G, Gp, max_components, nr_iterations, gain,
+                              threshold, cycle_fraction)
+        _check(lib.idg_clean(
+            pp, _np_ptr(residual, np.float32, "residual", True),
+            _np_ptr(psf, np.float32, "psf"),
+            None if mask is None else _np_ptr(mask, np.uint8, "mask"),
+            _np_ptr(model, np.float32, "model", True),
+            _np_ptr(components, COMPONENT_DTYPE, "components", True),
+            _np_ptr(state, STATE_DTYPE, "state", True)), "clean")
+        return residual, model, components, state
+    import torch
+    dev = residual.device
+    with _on_stream(stream):
+        if model is None:
+            model = torch.zeros((G, G), dtype=torch.float32, device=dev)
+        if components is None:
+            components = torch.zeros((records, 3), dtype=torch.int32,
+                                     device=dev)
+        if state is None:
+            state = torch.zeros(6, dtype=torch.int32, device=dev)
+    if (model.shape != residual.shape or components.numel() < 3 *
+            max_components or state.numel() != 6
+            or (mask is not None and mask.shape != residual.shape)):
+        raise ValueError("model and mask must be [G][G], components "
+                         "[max_components][3] int32, state [6] int32")
+    if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("mask must be uint8 or bool")
+    ptrs = (_dev_ptr(residual, "residual", torch.float32),
+            _dev_ptr(psf, "psf", torch.float32),
+            None if mask is None else _dev_ptr(mask, "mask"),
+            _dev_ptr(model, "model", torch.float32),
+            _dev_ptr(components, "components", torch.int32),
+            _dev_ptr(state, "state", torch.int32))
+    if check_every is not None and check_every < 1:
+        raise ValueError("check_every must be at least 1")
+    chunk = nr_iterations if check_every is None else check_every
+    left = nr_iterations
+    while True:
+        n = min(chunk, left)
+        p, pp = _clean_params(G, Gp, max_components, n, gain, threshold,
+                              cycle_fraction)
+        _check(lib.idg_clean_launch(pp, *ptrs, _stream_handle(stream)),
+               "clean")
+        left -= n
+        if left == 0:
+            break
+        with _on_stream(stream):    # the copy waits for `stream`, and only it
+            if int(state[1:2].cpu()) != 0:
+                break
+    return residual, model, components, state
 
 
 # ---------------------------------------------------------------------------
