@@ -1,4 +1,6 @@
-// idg_capi.cpp -- the extern "C" boundary (include/idg_mi355x.h).
+// idg_capi.cpp -- the extern "C" boundary (include/idg_mi355x.h): every entry
+// validates its arguments and calls the launch layer (hip/util.hpp) or a host
+// twin (host/host.hpp).
 #include "idg_mi355x.h"
 
 #include <hip/hip_runtime.h>
@@ -11,16 +13,16 @@
 #include <thread>
 #include <vector>
 
-#include "common/clean.hpp"
-#include "common/plan.hpp"
-#include "common/weight.hpp"
 #include "hip/util.hpp"
+#include "host/host.hpp"
 #include "lib-hip.hpp"
 
 static_assert(sizeof(idg_metadata_t) == sizeof(idg::Metadata),
               "metadata layout");
 static_assert(sizeof(idg_uvw_t) == sizeof(idg::UVWCoordinate<float>),
               "uvw layout");
+static_assert(sizeof(idg_cfloat_t) == sizeof(std::complex<float>),
+              "complex layout");
 
 namespace {
 
@@ -52,33 +54,42 @@ idg_mi355x::Problem make_problem(int nr_subgrids, int grid_size,
   return p;
 }
 
+// The struct_size rules of include/idg_mi355x.h for every versioned struct T
+// (`name`: its type name): *out = the caller's fields, zero-extended to this
+// library's struct; bytes of a newer, larger struct must be zero (a field
+// this library cannot honour).
+template <typename T>
+int read_struct(const T *in, const char *name, T *out) {
+  const std::string who = name;
+  if (in == nullptr) return fail(IDG_E_INVALID_ARGUMENT, who + ": null");
+  const uint32_t size = in->struct_size;
+  if (size < sizeof(uint32_t) || size % 4 != 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                who + ": struct_size " + std::to_string(size) +
+                    " (set it to sizeof(" + who + "), a multiple of 4)");
+  if (size > (1u << 16))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                who + ": struct_size " + std::to_string(size) + " is no " +
+                    who + " of any version");
+  std::memset(out, 0, sizeof *out);
+  std::memcpy(out, in, std::min<size_t>(size, sizeof *out));
+  const unsigned char *raw = reinterpret_cast<const unsigned char *>(in);
+  for (size_t i = sizeof *out; i < size; ++i)
+    if (raw[i] != 0)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  who + ": struct_size " + std::to_string(size) +
+                      " with a field set that this library (struct_size " +
+                      std::to_string(sizeof *out) + ") does not know");
+  return IDG_OK;
+}
+
 // idg_options_t -> idg_mi355x::Options (still a request: unset fields are
-// resolved from the environment where they are used).  The struct_size rules
-// of include/idg_mi355x.h.
+// resolved from the environment where they are used).  Null: all unset.
 int parse_options(const idg_options_t *o, idg_mi355x::Options *out) {
   *out = idg_mi355x::Options();
   if (o == nullptr) return IDG_OK;
-  const uint32_t size = o->struct_size;
-  if (size < sizeof(uint32_t) || size % 4 != 0)
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_options_t: struct_size " + std::to_string(size) +
-                    " (set it to sizeof(idg_options_t), a multiple of 4)");
-  if (size > (1u << 16))
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_options_t: struct_size " + std::to_string(size) +
-                    " is no idg_options_t of any version");
-  // the caller's fields, zero-extended to this library's struct; bytes of a
-  // newer, larger struct must be zero (an option this library cannot honour)
   idg_options_t v;
-  std::memset(&v, 0, sizeof v);
-  std::memcpy(&v, o, std::min<size_t>(size, sizeof v));
-  const unsigned char *raw = reinterpret_cast<const unsigned char *>(o);
-  for (size_t i = sizeof v; i < size; ++i)
-    if (raw[i] != 0)
-      return fail(IDG_E_INVALID_ARGUMENT,
-                  "idg_options_t: struct_size " + std::to_string(size) +
-                      " with a field set that this library (struct_size " +
-                      std::to_string(sizeof v) + ") does not know");
+  if (int rc = read_struct(o, "idg_options_t", &v)) return rc;
   if (v.gridder_impl > IDG_IMPL_AUTO)
     return fail(IDG_E_INVALID_ARGUMENT,
                 "idg_options_t: unknown gridder_impl " +
@@ -120,30 +131,15 @@ static_assert(IDG_IMPL_DEFAULT == idg_mi355x::kImplDefault &&
                   IDG_AUTO_THRESHOLD_DEFAULT == idg_mi355x::kAutoThreshold,
               "idg_options_t values are idg_mi355x::Options values");
 
-// idg_plan_params_t (struct_size rules of idg_options_t) and the sizes of a
-// plan call -> plan::Geometry without its scales, image_size and
-// 1 / w_step_in_lambda (computed here, once, for the host and the device).
+// idg_plan_params_t (read_struct) and the sizes of a plan call ->
+// plan::Geometry without its scales, image_size and 1 / w_step_in_lambda
+// (computed here, once, for the host and the device).
 int parse_plan(const idg_plan_params_t *params, int nr_baselines,
                int nr_timesteps, int nr_channels, int capacity,
                idg_mi355x::plan::Geometry *g, float *image_size,
                float *inv_w_step) {
-  if (params == nullptr)
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_plan_params_t: null");
-  const uint32_t size = params->struct_size;
-  if (size < sizeof(uint32_t) || size % 4 != 0 || size > (1u << 16))
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_plan_params_t: struct_size " + std::to_string(size) +
-                    " (set it to sizeof(idg_plan_params_t))");
   idg_plan_params_t v;
-  std::memset(&v, 0, sizeof v);
-  std::memcpy(&v, params, std::min<size_t>(size, sizeof v));
-  const unsigned char *raw = reinterpret_cast<const unsigned char *>(params);
-  for (size_t i = sizeof v; i < size; ++i)
-    if (raw[i] != 0)
-      return fail(IDG_E_INVALID_ARGUMENT,
-                  "idg_plan_params_t: struct_size " + std::to_string(size) +
-                      " with a field set that this library (struct_size " +
-                      std::to_string(sizeof v) + ") does not know");
+  if (int rc = read_struct(params, "idg_plan_params_t", &v)) return rc;
   if (nr_baselines < 1 || nr_timesteps < 1 || nr_channels < 1 || capacity < 0)
     return fail(IDG_E_INVALID_ARGUMENT,
                 "plan: nr_baselines, nr_timesteps, nr_channels >= 1 and "
@@ -176,8 +172,7 @@ int parse_plan(const idg_plan_params_t *params, int nr_baselines,
   return IDG_OK;
 }
 
-// idg_weight_params_t (struct_size rules of idg_options_t) and the sizes of a
-// weight call -> weight::Geometry, the scheme and (5 * 10^-robust)^2.
+// idg_weight_params_t (read_struct) and the sizes of a weight call -> weight::Geometry, the scheme and (5 * 10^-robust)^2.
 struct WeightCall {
   idg_mi355x::weight::Geometry g;
   int scheme = 0;
@@ -187,23 +182,8 @@ struct WeightCall {
 int parse_weight(const idg_weight_params_t *params, int nr_subgrids,
                  int subgrid_size, int nr_channels, WeightCall *out) {
   namespace wt = idg_mi355x::weight;
-  if (params == nullptr)
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_params_t: null");
-  const uint32_t size = params->struct_size;
-  if (size < sizeof(uint32_t) || size % 4 != 0 || size > (1u << 16))
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_weight_params_t: struct_size " + std::to_string(size) +
-                    " (set it to sizeof(idg_weight_params_t))");
   idg_weight_params_t v;
-  std::memset(&v, 0, sizeof v);
-  std::memcpy(&v, params, std::min<size_t>(size, sizeof v));
-  const unsigned char *raw = reinterpret_cast<const unsigned char *>(params);
-  for (size_t i = sizeof v; i < size; ++i)
-    if (raw[i] != 0)
-      return fail(IDG_E_INVALID_ARGUMENT,
-                  "idg_weight_params_t: struct_size " + std::to_string(size) +
-                      " with a field set that this library (struct_size " +
-                      std::to_string(sizeof v) + ") does not know");
+  if (int rc = read_struct(params, "idg_weight_params_t", &v)) return rc;
   if (nr_subgrids < 0 || subgrid_size < 1 || nr_channels < 1)
     return fail(IDG_E_INVALID_ARGUMENT,
                 "weight: nr_subgrids >= 0, subgrid_size >= 1 and "
@@ -236,61 +216,16 @@ static_assert(IDG_WEIGHT_NATURAL == idg_mi355x::weight::kNatural &&
                   IDG_WEIGHT_BRIGGS == idg_mi355x::weight::kBriggs,
               "idg_weight_params_t scheme values are weight:: values");
 
-// Row of timestep 0 of subgrid s (include/idg_mi355x.h).
-long long weight_row0(const idg_metadata_t *md, int s) {
-  return (static_cast<long long>(md[s].baseline_offset) -
-          md[0].baseline_offset) +
-         md[s].time_offset;
+// What a host twin (host/host.hpp) returns -> the entry's return value.
+int from_host(const idg_mi355x::host::Status &st) {
+  return st.code ? fail(st.code, st.message) : IDG_OK;
 }
 
-// Every record's rows inside [0, uvw_rows).
-int check_weight_rows(int nr_subgrids, size_t uvw_rows,
-                      const idg_metadata_t *md) {
-  for (int s = 0; s < nr_subgrids; ++s) {
-    const long long t0 = weight_row0(md, s);
-    if (md[s].nr_timesteps < 0 || t0 < 0 ||
-        t0 + md[s].nr_timesteps > static_cast<long long>(uvw_rows))
-      return fail(IDG_E_OUT_OF_BOUNDS,
-                  "subgrid " + std::to_string(s) + ": timesteps [" +
-                      std::to_string(t0) + ", " +
-                      std::to_string(t0 + md[s].nr_timesteps) +
-                      ") outside uvw/weight rows [0, " +
-                      std::to_string(uvw_rows) + ")");
-  }
-  return IDG_OK;
-}
-
-int check_density_cells(const idg_mi355x::weight::Geometry &g,
-                        const uint64_t *density) {
-  const size_t cells = static_cast<size_t>(g.grid_size) * g.grid_size;
-  for (size_t i = 0; i < cells; ++i)
-    if (density[i] >= idg_mi355x::weight::kCellLimit)
-      return fail(IDG_E_INVALID_ARGUMENT,
-                  "weight: density cell " + std::to_string(i) +
-                      " is at or above 2^62");
-  return IDG_OK;
-}
-
-// idg_clean_params_t (struct_size rules of idg_options_t) -> clean::Params.
+// idg_clean_params_t (read_struct) -> clean::Params.
 int parse_clean(const idg_clean_params_t *params,
                 idg_mi355x::clean::Params *out) {
-  if (params == nullptr)
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_clean_params_t: null");
-  const uint32_t size = params->struct_size;
-  if (size < sizeof(uint32_t) || size % 4 != 0 || size > (1u << 16))
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_clean_params_t: struct_size " + std::to_string(size) +
-                    " (set it to sizeof(idg_clean_params_t))");
   idg_clean_params_t v;
-  std::memset(&v, 0, sizeof v);
-  std::memcpy(&v, params, std::min<size_t>(size, sizeof v));
-  const unsigned char *raw = reinterpret_cast<const unsigned char *>(params);
-  for (size_t i = sizeof v; i < size; ++i)
-    if (raw[i] != 0)
-      return fail(IDG_E_INVALID_ARGUMENT,
-                  "idg_clean_params_t: struct_size " + std::to_string(size) +
-                      " with a field set that this library (struct_size " +
-                      std::to_string(sizeof v) + ") does not know");
+  if (int rc = read_struct(params, "idg_clean_params_t", &v)) return rc;
   if (v.psf_size < 1 || v.grid_size < v.psf_size ||
       v.grid_size > idg_mi355x::clean::kMaxGridSize)
     return fail(IDG_E_INVALID_ARGUMENT,
@@ -326,17 +261,32 @@ static_assert(IDG_CLEAN_RUNNING == idg_mi355x::clean::kRunning &&
                   sizeof(idg_clean_state_t) == 24,
               "idg_clean_* records are clean:: records");
 
-// The key of the residual's peak (clean::key_of; 0: none), row-major.
-uint64_t clean_peak(const idg_mi355x::clean::Params &p, const float *residual,
-                    const uint8_t *mask) {
-  const size_t cells = static_cast<size_t>(p.grid_size) * p.grid_size;
-  uint64_t best = 0;
-  for (size_t i = 0; i < cells; ++i) {
-    const uint64_t key = idg_mi355x::clean::key_of(
-        residual[i], static_cast<uint32_t>(i), mask == nullptr || mask[i] != 0);
-    if (key > best) best = key;
-  }
-  return best;
+// The null-buffer test that a host entry and its _launch twin (`entry`: which
+// of the two) share.
+int null_buffer(const char *entry, bool any_null) {
+  if (!any_null) return IDG_OK;
+  return fail(IDG_E_INVALID_ARGUMENT, std::string(entry) + ": null buffer");
+}
+int plan_buffers(const char *entry, const void *baselines, const void *uvw,
+                 const void *wavenumbers, const void *metadata, int capacity,
+                 const void *counts) {
+  return null_buffer(entry, !baselines || !uvw || !wavenumbers || !counts ||
+                                (capacity > 0 && !metadata));
+}
+int density_buffers(const char *entry, const void *metadata, const void *uvw,
+                    const void *wavenumbers, const void *weights,
+                    const void *density) {
+  return null_buffer(entry,
+                     !metadata || !uvw || !wavenumbers || !weights || !density);
+}
+int scheme_buffers(const char *entry, const void *density, const void *ab) {
+  return null_buffer(entry, !density || !ab);
+}
+int clean_buffers(const char *entry, const void *residual, const void *psf,
+                  const void *model, const void *components,
+                  const void *state) {
+  return null_buffer(entry,
+                     !residual || !psf || !model || !components || !state);
 }
 
 int check_geometry(const idg_mi355x::Problem &p) {
@@ -522,44 +472,12 @@ int idg_image_to_grid_launch(int grid_size, int nr_w_layers, float image_size,
 
 int idg_taper_to_image(int subgrid_size, int grid_size,
                        const float *spheroidal, double *out) {
-  const int S = subgrid_size, G = grid_size;
-  if (S < 1 || G < 1 || spheroidal == nullptr || out == nullptr)
+  if (subgrid_size < 1 || grid_size < 1 || spheroidal == nullptr ||
+      out == nullptr)
     return fail(IDG_E_INVALID_ARGUMENT,
                 "idg_taper_to_image: subgrid_size >= 1, grid_size >= 1 and "
                 "non-null buffers required");
-  // d[j][p]: the periodic interpolation kernel from sample p, at (p + 0.5 -
-  // S/2) subgrid pixels, to image pixel j, at (j - G/2) S / G of them;
-  // frequencies |k| < S/2 whole, the Nyquist pair (even S) as one cosine
-  const double two_pi = 6.283185307179586476925287;
-  std::vector<double> d(static_cast<size_t>(G) * S);
-  for (int j = 0; j < G; ++j)
-    for (int p = 0; p < S; ++p) {
-      const double delta = static_cast<double>(j - G / 2) * S / G -
-                           (static_cast<double>(p) + 0.5 - S / 2);
-      double sum = 1.0;
-      for (int k = 1; 2 * k < S; ++k)
-        sum += 2.0 * std::cos(two_pi * k * delta / S);
-      if (S % 2 == 0) sum += std::cos(0.5 * two_pi * delta);
-      d[static_cast<size_t>(j) * S + p] = sum / S;
-    }
-  // out = d taper d^T, the x sum first
-  std::vector<double> rows(static_cast<size_t>(S) * G);
-  for (int py = 0; py < S; ++py)
-    for (int j = 0; j < G; ++j) {
-      double sum = 0.0;
-      for (int px = 0; px < S; ++px)
-        sum += static_cast<double>(spheroidal[py * S + px]) *
-               d[static_cast<size_t>(j) * S + px];
-      rows[static_cast<size_t>(py) * G + j] = sum;
-    }
-  for (int i = 0; i < G; ++i)
-    for (int j = 0; j < G; ++j) {
-      double sum = 0.0;
-      for (int py = 0; py < S; ++py)
-        sum += d[static_cast<size_t>(i) * S + py] *
-               rows[static_cast<size_t>(py) * G + j];
-      out[static_cast<size_t>(i) * G + j] = sum;
-    }
+  idg_mi355x::host::taper_to_image(subgrid_size, grid_size, spheroidal, out);
   return IDG_OK;
 }
 
@@ -830,56 +748,15 @@ int idg_plan(const idg_plan_params_t *params, int nr_baselines,
   if (int rc = parse_plan(params, nr_baselines, nr_timesteps, nr_channels,
                           capacity, &g, &image_size, &inv_w_step))
     return rc;
-  if (!baselines || !uvw || !wavenumbers || !counts ||
-      (capacity > 0 && !metadata))
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_plan: null buffer");
-  idg_mi355x::plan::set_scales(&g, image_size, wavenumbers[0],
-                               wavenumbers[nr_channels - 1], inv_w_step);
-  const int B = nr_baselines, T = nr_timesteps;
-  const float *rows = reinterpret_cast<const float *>(uvw);
-  int32_t *out = reinterpret_cast<int32_t *>(metadata);
-  // count, prefix, fill: each pass splits the baselines over the threads
-  std::vector<int> count(B), dropped(B);
-  std::vector<long long> offset(B + 1, 0);
-  const auto pass = [&](bool fill) {
-    const int nt = std::max(1, std::min(nthreads, B));
-    const auto range = [&](int b0, int b1) {
-      for (int bl = b0; bl < b1; ++bl) {
-        const int row0 = bl * T;
-        int n = 0;
-        const long long first = offset[bl];
-        const int d = idg_mi355x::plan::walk_baseline(
-            g, rows + static_cast<size_t>(row0) * 3, row0, T,
-            baselines[2 * bl], baselines[2 * bl + 1],
-            [&](const int32_t words[9]) {
-              if (fill && first + n < capacity)
-                std::memcpy(out + (first + n) * 9, words, 9 * sizeof(int32_t));
-              ++n;
-            });
-        if (!fill) {
-          count[bl] = n;
-          dropped[bl] = d;
-        }
-      }
-    };
-    if (nt == 1) return range(0, B);
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) {
-      const int b0 = static_cast<int>(static_cast<long long>(B) * w / nt);
-      const int b1 = static_cast<int>(static_cast<long long>(B) * (w + 1) / nt);
-      if (b1 > b0) pool.emplace_back(range, b0, b1);
-    }
-    for (auto &th : pool) th.join();
-  };
-  pass(false);
-  long long lost = 0;
-  for (int bl = 0; bl < B; ++bl) {
-    offset[bl + 1] = offset[bl] + count[bl];
-    lost += dropped[bl];
-  }
-  counts[0] = static_cast<int32_t>(offset[B]);
-  counts[1] = static_cast<int32_t>(lost);
-  if (capacity > 0 && offset[B] > 0) pass(true);
+  if (int rc = plan_buffers("idg_plan", baselines, uvw, wavenumbers, metadata,
+                            capacity, counts))
+    return rc;
+  idg_mi355x::host::plan(g, image_size, inv_w_step, nr_baselines,
+                         nr_timesteps, nr_channels, baselines,
+                         reinterpret_cast<const idg_mi355x::host::UVW *>(uvw),
+                         wavenumbers,
+                         reinterpret_cast<idg::Metadata *>(metadata), capacity,
+                         counts, nthreads);
   return IDG_OK;
 }
 
@@ -893,9 +770,9 @@ int idg_plan_launch(const idg_plan_params_t *params, int nr_baselines,
   if (int rc = parse_plan(params, nr_baselines, nr_timesteps, nr_channels,
                           capacity, &g, &image_size, &inv_w_step))
     return rc;
-  if (!baselines || !uvw || !wavenumbers || !counts ||
-      (capacity > 0 && !metadata))
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_plan_launch: null buffer");
+  if (int rc = plan_buffers("idg_plan_launch", baselines, uvw, wavenumbers,
+                            metadata, capacity, counts))
+    return rc;
   return from_hip(idg_mi355x::launch_plan(
                       g, image_size, inv_w_step, nr_baselines, nr_timesteps,
                       nr_channels, baselines, uvw, wavenumbers, metadata,
@@ -908,41 +785,19 @@ int idg_weight_density(const idg_weight_params_t *params, int nr_subgrids,
                        const idg_metadata_t *metadata, const idg_uvw_t *uvw,
                        size_t uvw_rows, const float *wavenumbers,
                        const float *weights, uint64_t *density) {
-  namespace wt = idg_mi355x::weight;
   WeightCall call;
   if (int rc = parse_weight(params, nr_subgrids, subgrid_size, nr_channels,
                             &call))
     return rc;
   if (nr_subgrids == 0) return IDG_OK;
-  if (!metadata || !uvw || !wavenumbers || !weights || !density)
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_density: null buffer");
-  if (int rc = check_weight_rows(nr_subgrids, uvw_rows, metadata)) return rc;
-  if (int rc = check_density_cells(call.g, density)) return rc;
-  const size_t G = static_cast<size_t>(call.g.grid_size), C = nr_channels;
-  // summed on a copy, so that a failure leaves the caller's density alone
-  std::vector<uint64_t> sum(density, density + G * G);
-  for (int s = 0; s < nr_subgrids; ++s) {
-    const size_t row0 = static_cast<size_t>(weight_row0(metadata, s));
-    for (int t = 0; t < metadata[s].nr_timesteps; ++t) {
-      const size_t row = row0 + t;
-      for (size_t c = 0; c < C; ++c) {
-        int x, y;
-        const uint64_t q = wt::sample(call.g, uvw[row].u, uvw[row].v,
-                                      wavenumbers[c], weights[row * C + c],
-                                      &x, &y);
-        if (q == 0) continue;
-        uint64_t &cell = sum[static_cast<size_t>(y) * G + x];
-        cell += q;
-        if (cell >= wt::kCellLimit)
-          return fail(IDG_E_INVALID_ARGUMENT,
-                      "idg_weight_density: the sum of cell (" +
-                          std::to_string(x) + ", " + std::to_string(y) +
-                          ") reaches 2^62");
-      }
-    }
-  }
-  std::memcpy(density, sum.data(), G * G * sizeof(uint64_t));
-  return IDG_OK;
+  if (int rc = density_buffers("idg_weight_density", metadata, uvw,
+                               wavenumbers, weights, density))
+    return rc;
+  return from_host(idg_mi355x::host::weight_density(
+      call.g, nr_subgrids, nr_channels,
+      reinterpret_cast<const idg::Metadata *>(metadata),
+      reinterpret_cast<const idg_mi355x::host::UVW *>(uvw), uvw_rows,
+      wavenumbers, weights, density));
 }
 
 int idg_weight_density_launch(const idg_weight_params_t *params,
@@ -956,9 +811,9 @@ int idg_weight_density_launch(const idg_weight_params_t *params,
                             &call))
     return rc;
   if (nr_subgrids == 0) return IDG_OK;
-  if (!metadata || !uvw || !wavenumbers || !weights || !density)
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_weight_density_launch: null buffer");
+  if (int rc = density_buffers("idg_weight_density_launch", metadata, uvw,
+                               wavenumbers, weights, density))
+    return rc;
   return from_hip(idg_mi355x::launch_weight_density(
                       call.g, nr_subgrids, subgrid_size, nr_channels, metadata,
                       uvw, wavenumbers, weights, density,
@@ -968,25 +823,11 @@ int idg_weight_density_launch(const idg_weight_params_t *params,
 
 int idg_weight_scheme(const idg_weight_params_t *params,
                       const uint64_t *density, float ab[2]) {
-  namespace wt = idg_mi355x::weight;
   WeightCall call;
   if (int rc = parse_weight(params, 0, 1, 1, &call)) return rc;
-  if (!density || !ab)
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_scheme: null buffer");
-  if (int rc = check_density_cells(call.g, density)) return rc;
-  double sum_d = 0.0, sum_d2 = 0.0;
-  if (call.scheme == wt::kBriggs) {
-    const int G = call.g.grid_size;
-    for (int y = 0; y < G; ++y)
-      for (int x = 0; x < G; ++x) {
-        const double D = wt::density_of(wt::count_at(call.g, density, x, y),
-                                        call.g.quantum_log2);
-        sum_d += D;
-        sum_d2 += D * D;
-      }
-  }
-  wt::scheme_ab(call.scheme, call.briggs_scale, sum_d, sum_d2, &ab[0], &ab[1]);
-  return IDG_OK;
+  if (int rc = scheme_buffers("idg_weight_scheme", density, ab)) return rc;
+  return from_host(idg_mi355x::host::weight_scheme(
+      call.g, call.scheme, call.briggs_scale, density, ab));
 }
 
 int idg_weight_scheme_launch(const idg_weight_params_t *params,
@@ -994,9 +835,8 @@ int idg_weight_scheme_launch(const idg_weight_params_t *params,
                              void *stream) {
   WeightCall call;
   if (int rc = parse_weight(params, 0, 1, 1, &call)) return rc;
-  if (!density || !ab)
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_weight_scheme_launch: null buffer");
+  if (int rc = scheme_buffers("idg_weight_scheme_launch", density, ab))
+    return rc;
   return from_hip(idg_mi355x::launch_weight_scheme(
                       call.g, call.scheme, call.briggs_scale, density, ab,
                       static_cast<hipStream_t>(stream)),
@@ -1010,7 +850,6 @@ int idg_weight_apply(const idg_weight_params_t *params, int nr_subgrids,
                      const uint64_t *density, const float ab[2],
                      const idg_cfloat_t *visibilities, float *imaging_weights,
                      idg_cfloat_t *out, double *sum_weights) {
-  namespace wt = idg_mi355x::weight;
   WeightCall call;
   if (int rc = parse_weight(params, nr_subgrids, 1, nr_channels, &call))
     return rc;
@@ -1023,45 +862,14 @@ int idg_weight_apply(const idg_weight_params_t *params, int nr_subgrids,
   if (!metadata || !uvw || !wavenumbers || !weights || !density || !ab ||
       !imaging_weights || !out)
     return fail(IDG_E_INVALID_ARGUMENT, "idg_weight_apply: null buffer");
-  if (int rc = check_weight_rows(nr_subgrids, uvw_rows, metadata)) return rc;
-  if (int rc = check_density_cells(call.g, density)) return rc;
-  const size_t C = nr_channels;
-  const float a = ab[0], b = ab[1];
-  double sum = 0.0;
-  for (int s = 0; s < nr_subgrids; ++s) {
-    const size_t row0 = static_cast<size_t>(weight_row0(metadata, s));
-    for (int t = 0; t < metadata[s].nr_timesteps; ++t) {
-      const size_t row = row0 + t;
-      for (size_t c = 0; c < C; ++c) {
-        const size_t at = row * C + c;
-        const float w = weights[at];
-        int x, y;
-        const bool live = wt::sample(call.g, uvw[row].u, uvw[row].v,
-                                     wavenumbers[c], w, &x, &y) != 0;
-        const float f =
-            live ? wt::imaging_weight(
-                       w, a, b,
-                       wt::density_of(wt::count_at(call.g, density, x, y),
-                                      call.g.quantum_log2))
-                 : 0.0f;
-        idg_cfloat_t *o = out + at * 4;
-        if (visibilities == nullptr) {
-          o[0] = o[3] = idg_cfloat_t{f, 0.0f};
-          o[1] = o[2] = idg_cfloat_t{0.0f, 0.0f};
-        } else if (live) {
-          const idg_cfloat_t *v = visibilities + at * 4;
-          for (int p = 0; p < 4; ++p)
-            o[p] = idg_cfloat_t{f * v[p].re, f * v[p].im};
-        } else {
-          for (int p = 0; p < 4; ++p) o[p] = idg_cfloat_t{0.0f, 0.0f};
-        }
-        imaging_weights[at] = f;
-        sum += f;
-      }
-    }
-  }
-  *sum_weights = sum;
-  return IDG_OK;
+  return from_host(idg_mi355x::host::weight_apply(
+      call.g, nr_subgrids, nr_channels,
+      reinterpret_cast<const idg::Metadata *>(metadata),
+      reinterpret_cast<const idg_mi355x::host::UVW *>(uvw), uvw_rows,
+      wavenumbers, weights, density, ab,
+      reinterpret_cast<const std::complex<float> *>(visibilities),
+      imaging_weights, reinterpret_cast<std::complex<float> *>(out),
+      sum_weights));
 }
 
 int idg_weight_apply_launch(const idg_weight_params_t *params, int nr_subgrids,
@@ -1099,37 +907,14 @@ int idg_clean(const idg_clean_params_t *params, float *residual,
   namespace cl = idg_mi355x::clean;
   cl::Params p;
   if (int rc = parse_clean(params, &p)) return rc;
-  if (!residual || !psf || !model || !components || !state)
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_clean: null buffer");
-  cl::State s;
-  std::memcpy(&s, state, sizeof s);
-  if (!cl::state_ok(s, p))
-    return fail(IDG_E_INVALID_ARGUMENT,
-                "idg_clean: state.n_components " +
-                    std::to_string(s.n_components) + " outside [0, " +
-                    std::to_string(p.max_components) + "]");
-  const size_t G = static_cast<size_t>(p.grid_size);
-  const size_t Gp = static_cast<size_t>(p.psf_size);
-  uint64_t key = 0;
-  for (int k = 0;; ++k) {
-    key = clean_peak(p, residual, mask);
-    if (k == p.nr_iterations) break;
-    float c = 0.0f;
-    const uint32_t index = key != 0 ? cl::index_of(key) : 0;
-    if (!cl::step(&s, p, key, key != 0 ? residual[index] : 0.0f, &c)) break;
-    const int py = static_cast<int>(index / G), px = static_cast<int>(index % G);
-    components[s.n_components - 1] = {py, px, c};
-    model[index] = model[index] + c;
-    const cl::Patch pt = cl::patch_of(p, py, px);
-    for (int y = pt.y0; y < pt.y1; ++y) {
-      float *row = residual + static_cast<size_t>(y) * G;
-      const float *prow = psf + static_cast<size_t>(y - pt.oy) * Gp;
-      for (int x = pt.x0; x < pt.x1; ++x)
-        row[x] = cl::subtract(c, prow[x - pt.ox], row[x]);
-    }
-  }
-  cl::set_peak(&s, key);
-  std::memcpy(state, &s, sizeof s);
+  if (int rc = clean_buffers("idg_clean", residual, psf, model, components,
+                             state))
+    return rc;
+  const std::string msg = idg_mi355x::host::clean(
+      p, residual, psf, mask, model,
+      reinterpret_cast<cl::Component *>(components),
+      reinterpret_cast<cl::State *>(state));
+  if (!msg.empty()) return fail(IDG_E_INVALID_ARGUMENT, msg);
   return IDG_OK;
 }
 
@@ -1139,8 +924,9 @@ int idg_clean_launch(const idg_clean_params_t *params, float *residual,
                      idg_clean_state_t *state, void *stream) {
   idg_mi355x::clean::Params p;
   if (int rc = parse_clean(params, &p)) return rc;
-  if (!residual || !psf || !model || !components || !state)
-    return fail(IDG_E_INVALID_ARGUMENT, "idg_clean_launch: null buffer");
+  if (int rc = clean_buffers("idg_clean_launch", residual, psf, model,
+                             components, state))
+    return rc;
   return from_hip(idg_mi355x::launch_clean(p, residual, psf, mask, model,
                                            components, state,
                                            static_cast<hipStream_t>(stream)),

@@ -1,6 +1,6 @@
 // clean.hpp -- the arithmetic of the Hogbom minor cycle: the
 // order of peaks, the stop decision of one iteration and the subtraction of
-// one pixel.  Shared by the host entry (idg_clean; capi/idg_capi.cpp) and the
+// one pixel.  Shared by the host twin (host::clean; host/clean.cpp) and the
 // device kernels (hip/kernels/clean_mi355x.hip.cpp), whose outputs are bit
 // for bit the same: every float operation below is one rounded float32
 // operation (the library is built -ffp-contract=off), the one fused operation

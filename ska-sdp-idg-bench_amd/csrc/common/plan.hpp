@@ -1,6 +1,6 @@
 // plan.hpp -- the plan step's arithmetic: uvw rows of one
 // baseline -> subgrids (row range, A-term slot, w layer, corner).  Shared by
-// the host entry (idg_plan, capi/idg_capi.cpp) and the device kernels
+// the host twin (host::plan, host/plan.cpp) and the device kernels
 // (hip/kernels/plan_mi355x.hip.cpp), whose outputs are bit for bit the same:
 // every float operation below is one rounded float32 operation (the library
 // is built -ffp-contract=off), there is no division, and everything after the

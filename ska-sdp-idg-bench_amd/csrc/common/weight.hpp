@@ -1,7 +1,7 @@
 // weight.hpp -- the imaging-weight arithmetic: the uv cell of
 // a sample, its quantised weight q, the density D at a cell and the imaging
-// weight f = w / (a + b D).  Shared by the host entries (idg_weight_density,
-// idg_weight_scheme, idg_weight_apply; capi/idg_capi.cpp) and the device
+// weight f = w / (a + b D).  Shared by the host twins (host::weight_density,
+// weight_scheme, weight_apply; host/weight.cpp) and the device
 // kernels (hip/kernels/weight_mi355x.hip.cpp), whose outputs are bit for bit
 // the same: every float operation below is one rounded float32 operation (the
 // library is built -ffp-contract=off), the density is a sum of integers.

@@ -82,7 +82,8 @@ void print_benchmark();
 
 // ---------------------------------------------------------------------------
 // MI355X runtime: kernel selection, validation and raw-pointer pipelines.
-// Used by the kernel TUs, by util.cpp and by the C ABI (capi/idg_capi.cpp).
+// Used by the kernel TUs, by util.cpp and by the C ABI (capi/idg_capi.cpp);
+// the host twins of launch_plan, _weight_* and _clean are in host/host.hpp.
 // ---------------------------------------------------------------------------
 namespace idg_mi355x {
 

@@ -1,0 +1,76 @@
+// host.hpp -- the host twins of the device steps: the plan walk, the imaging
+// weights, the Hogbom minor cycle and the taper's image.  Plain C++ over the
+// per-element rules of common/{plan,weight,clean}.hpp, no HIP call, so they
+// run (and compile) without a GPU; the GPU suites compare the device kernels
+// against them bit for bit.  Each takes the parsed values its launch_*
+// counterpart (hip/util.hpp) takes; the C ABI (capi/idg_capi.cpp) validates
+// the arguments, calls one of them and reports what it returns.
+#pragma once
+
+#include <complex>
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "common/clean.hpp"
+#include "common/plan.hpp"
+#include "common/types.hpp"
+#include "common/weight.hpp"
+
+namespace idg_mi355x {
+namespace host {
+
+using UVW = idg::UVWCoordinate<float>;
+
+// An IDG_E_* code of include/idg_mi355x.h and its message; 0: success.
+struct Status {
+  int code = 0;
+  std::string message;
+};
+
+// host/plan.cpp.  The count, prefix and fill passes over
+// nr_baselines x nr_timesteps uvw rows, the baselines split over at most
+// `nthreads` threads (the bytes do not depend on it): counts = {subgrids
+// needed, dropped timesteps}; records past `capacity` are not written.
+void plan(plan::Geometry geometry, float image_size, float inv_w_step,
+          int nr_baselines, int nr_timesteps, int nr_channels,
+          const uint32_t *baselines, const UVW *uvw, const float *wavenumbers,
+          idg::Metadata *metadata, int capacity, int32_t counts[2],
+          int nthreads);
+
+// host/weight.cpp.  IDG_E_OUT_OF_BOUNDS: a record's rows
+// outside [0, uvw_rows); IDG_E_INVALID_ARGUMENT: a density cell at or above
+// 2^62, on entry or (weight_density, which then leaves `density` as it was)
+// while summing.  They check rows first, then cells.
+Status weight_density(const weight::Geometry &geometry, int nr_subgrids,
+                      int nr_channels, const idg::Metadata *metadata,
+                      const UVW *uvw, size_t uvw_rows,
+                      const float *wavenumbers, const float *weights,
+                      uint64_t *density);
+Status weight_scheme(const weight::Geometry &geometry, int scheme,
+                     double briggs_scale, const uint64_t *density,
+                     float ab[2]);
+// visibilities null: out = (f, 0, 0, f).
+Status weight_apply(const weight::Geometry &geometry, int nr_subgrids,
+                    int nr_channels, const idg::Metadata *metadata,
+                    const UVW *uvw, size_t uvw_rows, const float *wavenumbers,
+                    const float *weights, const uint64_t *density,
+                    const float ab[2],
+                    const std::complex<float> *visibilities,
+                    float *imaging_weights, std::complex<float> *out,
+                    double *sum_weights);
+
+// host/clean.cpp.  params.nr_iterations iterations from
+// *state; mask may be null.  Not empty: the state no iteration may run from
+// (clean::state_ok), every buffer left as it was.
+std::string clean(const clean::Params &params, float *residual,
+                  const float *psf, const uint8_t *mask, float *model,
+                  clean::Component *components, clean::State *state);
+
+// host/image.cpp.  out[G][G]: the [S][S] taper interpolated
+// to the image's pixels, in doubles.
+void taper_to_image(int subgrid_size, int grid_size, const float *spheroidal,
+                    double *out);
+
+}  // namespace host
+}  // namespace idg_mi355x
