@@ -715,6 +715,94 @@ int idg_clean_launch(const idg_clean_params_t *params, float *residual,
                      idg_clean_component_t *components,
                      idg_clean_state_t *state, void *stream);
 
+/* ---- restore: clean beam and restored image --------------------
+ * model and residual -> the image an imager hands over: the model convolved
+ * with a Gaussian clean beam fitted to the PSF's main lobe, plus the residual.
+ * No reference counterpart.  All planes are single float32 [G][G] planes (the
+ * Stokes-I convention of the CLEAN entries).  Three parts: the beam fit and
+ * the tap table are host only, tiny and in doubles; the restore itself has a
+ * host form and a _launch form that produce the same bytes.
+ *
+ * Beam.  exp(-(a dx^2 + 2 b dx dy + c dy^2)), dx and dy in pixels, peak 1: a
+ * component of flux f restores to a peak of f.  major >= minor: the FWHMs in
+ * pixels along the eigen-directions of the form, 2 sqrt(ln 2 / lambda).  pa:
+ * the angle of the major axis from +x towards +y, in (-pi/2, pi/2].
+ * idg_beam_from_axes fills a, b, c from the three numbers (major >= minor >
+ * 0, pa finite; pa is brought into the range); idg_beam_fit fills all six.
+ * Both read beam->struct_size (the rules of idg_options_t) and write the
+ * fields it has room for.  idg_beam_radius and idg_beam_taps read a, b, c only.
+ *
+ * Fit.  idg_beam_fit(psf_size = Gp, psf [Gp][Gp], level, beam): host
+ * pointers, no device.  Centre (Gp / 2, Gp / 2); p0 = psf[centre] must be
+ * finite and > 0; q = (double)psf / (double)p0.  Region: the pixels with
+ * q >= level that are 4-connected to the centre through such pixels, inside
+ * the psf and within |dy|, |dx| <= 32 (0 < level < 1; 0.5 is the usual
+ * choice); a sidelobe above the level that is not connected to the centre is
+ * left out.  Over the region in row-major order, in doubles, the 3 x 3 normal
+ * equations of min sum w (a dx^2 + b2 dx dy + c dy^2 + ln q)^2 with w = q^2
+ * and b2 = 2 b (the weights make the log-linear fit approximate the
+ * least-squares fit of the Gaussian itself), solved by elimination.
+ * IDG_E_INVALID_ARGUMENT, *beam untouched, idg_last_error() saying which: a
+ * bad struct_size; a NULL pointer, psf_size < 1 or level outside (0, 1); a
+ * centre not finite and positive; fewer than three region pixels besides the
+ * centre; a region that touches the +-32 window's edge (lobe too wide); a
+ * singular or non-finite system; a solution with a <= 0, c <= 0 or
+ * a c - b^2 <= 0.
+ *
+ * Taps.  idg_beam_radius returns floor(sqrt(-ln(cutoff) / lambda_min)), the
+ * largest integer distance along the major axis at which the beam is still
+ * >= cutoff; IDG_E_INVALID_ARGUMENT if cutoff is not in (0, 1), the beam's
+ * form is not positive definite or the result exceeds 32.  idg_beam_taps
+ * writes taps[dy + R][dx + R] = (float)exp(-(a dx^2 + 2 b dx dy + c dy^2)),
+ * 0 <= R <= 32: the exponent in doubles in exactly that association (dx^2,
+ * dx dy and dy^2 are exact integers), libm exp.  The taps are an input of the
+ * restore, as psf is an input of idg_clean: both forms read the same table.
+ *
+ * Restore.  model, residual (NULL: none), restored: float32 [G][G], 1 <= G <=
+ * 16384; taps: float32 [2R + 1][2R + 1], 0 <= R <= 32.  For every (y, x):
+ *   acc = +0.0f
+ *   for (y', x') in row-major order, |y - y'| <= R, |x - x'| <= R, inside the
+ *   image:
+ *     m = model[y'][x'];  if (m == 0.0f) continue;     (+-0 skipped, NaN taken)
+ *     acc = fmaf(m, taps[y - y' + R][x - x' + R], acc)
+ *   restored[y][x] = (residual ? residual[y][x] : 0.0f) + acc   (one add)
+ * The skip is part of the contract: with it the bytes do not depend on
+ * whether an implementation visits the zero pixels, even for non-finite taps.
+ * restored may be the same pointer as residual (a pixel reads only its own
+ * residual).  IDG_E_INVALID_ARGUMENT, every buffer left as it was: a bad
+ * struct_size, a size out of range, a NULL model, taps or restored, any other
+ * overlap among the four buffers, and (host form) a tap that is not finite.
+ * idg_restore takes host pointers and needs no device; its cost follows the
+ * number of non-zero model pixels. */
+typedef struct idg_beam_t {
+  uint32_t struct_size; /* sizeof(idg_beam_t)                                */
+  double a, b, c;
+  double major, minor, pa;
+} idg_beam_t;
+
+typedef struct idg_restore_params_t {
+  uint32_t struct_size; /* sizeof(idg_restore_params_t)                      */
+  int32_t grid_size;    /* G                                                 */
+  int32_t radius;       /* R                                                 */
+} idg_restore_params_t;
+
+int idg_beam_from_axes(double major, double minor, double pa,
+                       idg_beam_t *beam);
+int idg_beam_fit(int psf_size, const float *psf, float level,
+                 idg_beam_t *beam);
+/* >= 0: the radius. */
+int idg_beam_radius(const idg_beam_t *beam, double cutoff);
+int idg_beam_taps(const idg_beam_t *beam, int radius, float *taps);
+
+int idg_restore(const idg_restore_params_t *params, const float *model,
+                const float *residual, const float *taps, float *restored);
+/* Device pointers; asynchronous on `stream`: one launch, nothing read back,
+ * no synchronisation, nothing allocated.  It cannot read the taps, so a tap
+ * that is not finite is not refused here: it goes into the sums as it is. */
+int idg_restore_launch(const idg_restore_params_t *params, const float *model,
+                       const float *residual, const float *taps,
+                       float *restored, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

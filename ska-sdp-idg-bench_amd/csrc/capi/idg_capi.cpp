@@ -261,6 +261,76 @@ static_assert(IDG_CLEAN_RUNNING == idg_mi355x::clean::kRunning &&
                   sizeof(idg_clean_state_t) == 24,
               "idg_clean_* records are clean:: records");
 
+// idg_beam_t (read_struct) -> host::Beam; `who`: the entry.  The form must be
+// positive definite.
+int parse_beam(const idg_beam_t *beam, const char *who,
+               idg_mi355x::host::Beam *out) {
+  idg_beam_t v;
+  if (int rc = read_struct(beam, "idg_beam_t", &v)) return rc;
+  const idg_mi355x::host::Beam b = {v.a, v.b, v.c, v.major, v.minor, v.pa};
+  if (!idg_mi355x::host::beam_ok(b))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                std::string(who) + ": a, b, c must be finite with a > 0, "
+                                   "c > 0 and a c - b^2 > 0");
+  *out = b;
+  return IDG_OK;
+}
+
+// A beam back to the caller's idg_beam_t (already through read_struct): the
+// fields its struct_size has room for; struct_size stays the caller's.
+void store_beam(const idg_mi355x::host::Beam &b, idg_beam_t *beam) {
+  idg_beam_t v;
+  std::memset(&v, 0, sizeof v);
+  v.struct_size = beam->struct_size;
+  v.a = b.a, v.b = b.b, v.c = b.c;
+  v.major = b.major, v.minor = b.minor, v.pa = b.pa;
+  std::memcpy(beam, &v, std::min<size_t>(v.struct_size, sizeof v));
+}
+
+// idg_restore_params_t (read_struct) and the buffers of a restore call
+// (`entry`: which of the two) -> restore::Params.  Pointer values only: the
+// _launch form's are device pointers.
+int parse_restore(const char *entry, const idg_restore_params_t *params,
+                  const float *model, const float *residual,
+                  const float *taps, const float *restored,
+                  idg_mi355x::restore::Params *out) {
+  namespace rs = idg_mi355x::restore;
+  idg_restore_params_t v;
+  if (int rc = read_struct(params, "idg_restore_params_t", &v)) return rc;
+  if (v.grid_size < 1 || v.grid_size > rs::kMaxGridSize || v.radius < 0 ||
+      v.radius > rs::kMaxRadius)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "restore: 1 <= grid_size <= 16384 and 0 <= radius <= 32 "
+                "required");
+  if (!model || !taps || !restored)
+    return fail(IDG_E_INVALID_ARGUMENT, std::string(entry) + ": null buffer");
+  const size_t plane = sizeof(float) * v.grid_size * v.grid_size;
+  const size_t side = 2 * static_cast<size_t>(v.radius) + 1;
+  struct Span {
+    const char *name;
+    uintptr_t at;
+    size_t bytes;
+  };
+  const Span spans[4] = {
+      {"model", reinterpret_cast<uintptr_t>(model), plane},
+      {"residual", reinterpret_cast<uintptr_t>(residual), plane},
+      {"taps", reinterpret_cast<uintptr_t>(taps), sizeof(float) * side * side},
+      {"restored", reinterpret_cast<uintptr_t>(restored), plane}};
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j) {
+      const Span &a = spans[i], &b = spans[j];
+      if (a.at == 0 || b.at == 0) continue;  // (no residual)
+      if (i == 1 && j == 3 && a.at == b.at) continue;  // restored is residual
+      if (a.at < b.at + b.bytes && b.at < a.at + a.bytes)
+        return fail(IDG_E_INVALID_ARGUMENT,
+                    std::string(entry) + ": " + a.name + " and " + b.name +
+                        " overlap (only restored == residual may)");
+    }
+  out->grid_size = v.grid_size;
+  out->radius = v.radius;
+  return IDG_OK;
+}
+
 // The null-buffer test that a host entry and its _launch twin (`entry`: which
 // of the two) share.
 int null_buffer(const char *entry, bool any_null) {
@@ -931,6 +1001,89 @@ int idg_clean_launch(const idg_clean_params_t *params, float *residual,
                                            components, state,
                                            static_cast<hipStream_t>(stream)),
                   "idg_clean_launch");
+}
+
+int idg_beam_from_axes(double major, double minor, double pa,
+                       idg_beam_t *beam) {
+  idg_beam_t size_only;
+  if (int rc = read_struct(beam, "idg_beam_t", &size_only)) return rc;
+  idg_mi355x::host::Beam b;
+  const std::string msg = idg_mi355x::host::beam_from_axes(major, minor, pa, &b);
+  if (!msg.empty()) return fail(IDG_E_INVALID_ARGUMENT, msg);
+  store_beam(b, beam);
+  return IDG_OK;
+}
+
+int idg_beam_fit(int psf_size, const float *psf, float level,
+                 idg_beam_t *beam) {
+  idg_beam_t size_only;
+  if (int rc = read_struct(beam, "idg_beam_t", &size_only)) return rc;
+  if (psf == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_beam_fit: null buffer");
+  if (psf_size < 1 || !(level > 0.0f) || !(level < 1.0f))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_beam_fit: psf_size >= 1 and 0 < level < 1 required");
+  idg_mi355x::host::Beam b;
+  const std::string msg = idg_mi355x::host::beam_fit(psf_size, psf, level, &b);
+  if (!msg.empty()) return fail(IDG_E_INVALID_ARGUMENT, msg);
+  store_beam(b, beam);
+  return IDG_OK;
+}
+
+int idg_beam_radius(const idg_beam_t *beam, double cutoff) {
+  idg_mi355x::host::Beam b;
+  if (int rc = parse_beam(beam, "idg_beam_radius", &b)) return rc;
+  if (!(cutoff > 0.0) || !(cutoff < 1.0))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_beam_radius: 0 < cutoff < 1 required");
+  const double reach = idg_mi355x::host::beam_reach(b, cutoff);
+  if (!(reach <= idg_mi355x::restore::kMaxRadius))
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_beam_radius: the beam is above the cutoff beyond 32 "
+                "pixels");
+  return static_cast<int>(reach);
+}
+
+int idg_beam_taps(const idg_beam_t *beam, int radius, float *taps) {
+  idg_mi355x::host::Beam b;
+  if (int rc = parse_beam(beam, "idg_beam_taps", &b)) return rc;
+  if (radius < 0 || radius > idg_mi355x::restore::kMaxRadius)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_beam_taps: 0 <= radius <= 32 required");
+  if (taps == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_beam_taps: null buffer");
+  idg_mi355x::host::beam_taps(b, radius, taps);
+  return IDG_OK;
+}
+
+int idg_restore(const idg_restore_params_t *params, const float *model,
+                const float *residual, const float *taps, float *restored) {
+  idg_mi355x::restore::Params p;
+  if (int rc = parse_restore("idg_restore", params, model, residual, taps,
+                             restored, &p))
+    return rc;
+  const int side = 2 * p.radius + 1;
+  for (int i = 0; i < side * side; ++i)
+    if (!std::isfinite(taps[i]))
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "idg_restore: tap " + std::to_string(i) + " is not finite");
+  const std::string msg =
+      idg_mi355x::host::restore(p, model, residual, taps, restored);
+  if (!msg.empty()) return fail(static_cast<int>(hipErrorOutOfMemory), msg);
+  return IDG_OK;
+}
+
+int idg_restore_launch(const idg_restore_params_t *params, const float *model,
+                       const float *residual, const float *taps,
+                       float *restored, void *stream) {
+  idg_mi355x::restore::Params p;
+  if (int rc = parse_restore("idg_restore_launch", params, model, residual,
+                             taps, restored, &p))
+    return rc;
+  return from_hip(idg_mi355x::launch_restore(p, model, residual, taps,
+                                             restored,
+                                             static_cast<hipStream_t>(stream)),
+                  "idg_restore_launch");
 }
 
 double idg_p_run_gridder(void) {

@@ -83,7 +83,8 @@ void print_benchmark();
 // ---------------------------------------------------------------------------
 // MI355X runtime: kernel selection, validation and raw-pointer pipelines.
 // Used by the kernel TUs, by util.cpp and by the C ABI (capi/idg_capi.cpp);
-// the host twins of launch_plan, _weight_* and _clean are in host/host.hpp.
+// the host twins of launch_plan, _weight_*, _clean and _restore are in
+// host/host.hpp.
 // ---------------------------------------------------------------------------
 namespace idg_mi355x {
 
@@ -368,6 +369,17 @@ hipError_t launch_clean(const clean::Params &params, float *d_residual,
                         const float *d_psf, const uint8_t *d_mask,
                         float *d_model, void *d_components, void *d_state,
                         hipStream_t stream);
+
+// The restore step on the device (kernels/restore_mi355x.hip.cpp; DESIGN.md
+// §16), bit for bit the host entry of common/restore.hpp's arithmetic: one
+// launch, one workgroup per tile, no workspace; nothing is read back.
+// d_residual may be null, and d_restored may be d_residual.
+namespace restore {
+struct Params;
+}
+hipError_t launch_restore(const restore::Params &params, const float *d_model,
+                          const float *d_residual, const float *d_taps,
+                          float *d_restored, hipStream_t stream);
 
 // Returns an empty string if every subgrid's time range, stations and A-term
 // slot lie inside the buffers, else a description of the first violation.

@@ -1,6 +1,7 @@
 // host.hpp -- the host twins of the device steps: the plan walk, the imaging
-// weights, the Hogbom minor cycle and the taper's image.  Plain C++ over the
-// per-element rules of common/{plan,weight,clean}.hpp, no HIP call, so they
+// weights, the Hogbom minor cycle, the restore step and the taper's image.
+// Plain C++ over the per-element rules of
+// common/{plan,weight,clean,restore}.hpp, no HIP call, so they
 // run (and compile) without a GPU; the GPU suites compare the device kernels
 // against them bit for bit.  Each takes the parsed values its launch_*
 // counterpart (hip/util.hpp) takes; the C ABI (capi/idg_capi.cpp) validates
@@ -14,6 +15,7 @@
 
 #include "common/clean.hpp"
 #include "common/plan.hpp"
+#include "common/restore.hpp"
 #include "common/types.hpp"
 #include "common/weight.hpp"
 
@@ -66,6 +68,30 @@ Status weight_apply(const weight::Geometry &geometry, int nr_subgrids,
 std::string clean(const clean::Params &params, float *residual,
                   const float *psf, const uint8_t *mask, float *model,
                   clean::Component *components, clean::State *state);
+
+// host/restore.cpp.  The clean beam exp(-(a dx^2 + 2 b dx dy +
+// c dy^2)) with its FWHMs and the major axis' angle (idg_beam_t without its
+// struct_size); all of it in doubles, host only.
+struct Beam {
+  double a, b, c;
+  double major, minor, pa;
+};
+// a, b, c finite and the form positive definite.
+bool beam_ok(const Beam &beam);
+// Not empty: the refusal, *out untouched.
+std::string beam_from_axes(double major, double minor, double pa, Beam *out);
+std::string beam_fit(int psf_size, const float *psf, float level, Beam *out);
+// floor(sqrt(-ln(cutoff) / the smaller eigenvalue)), as a double.
+double beam_reach(const Beam &beam, double cutoff);
+// taps[2 radius + 1][2 radius + 1]; dx^2, dx dy and dy^2 are exact integers.
+void beam_taps(const Beam &beam, int radius, float *taps);
+// The restore step: the non-zero model pixels in row-major order, each one's
+// footprint added onto an accumulator plane, then the add of the residual
+// (null: none).  Its cost follows the number of non-zero pixels.  Not empty:
+// no memory for the accumulator, nothing written.
+std::string restore(const restore::Params &params, const float *model,
+                    const float *residual, const float *taps,
+                    float *restored);
 
 // host/image.cpp.  out[G][G]: the [S][S] taper interpolated
 // to the image's pixels, in doubles.

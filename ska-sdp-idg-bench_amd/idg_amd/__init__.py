@@ -20,9 +20,11 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   predict, taper_to_image,
                   psf, weigh, weight_apply, weight_density, weight_scheme,
                   CLEAN_REASONS, COMPONENT_DTYPE, STATE_DTYPE, clean,
-                  model_image, stokes_i)
-from ._lib import (LIB_PATH, CleanParamsStruct, OptionsStruct,
-                   PlanParamsStruct, WeightParamsStruct)
+                  model_image, stokes_i,
+                  Beam, beam_fit, beam_from_axes, beam_radius, beam_taps,
+                  restore)
+from ._lib import (LIB_PATH, BeamStruct, CleanParamsStruct, OptionsStruct,
+                   PlanParamsStruct, RestoreParamsStruct, WeightParamsStruct)
 from . import shard
 
 __all__ = [
@@ -42,4 +44,6 @@ __all__ = [
     "WeightParamsStruct",
     "CLEAN_REASONS", "COMPONENT_DTYPE", "STATE_DTYPE", "clean", "model_image",
     "stokes_i", "CleanParamsStruct",
+    "Beam", "beam_fit", "beam_from_axes", "beam_radius", "beam_taps",
+    "restore", "BeamStruct", "RestoreParamsStruct",
 ]

@@ -84,6 +84,12 @@ SIGNATURES = {
                                      _P, _P, _P, _P]),
     "idg_clean": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "idg_clean_launch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "idg_beam_from_axes": (_I, [_D, _D, _D, _P]),
+    "idg_beam_fit": (_I, [_I, _P, _F, _P]),
+    "idg_beam_radius": (_I, [_P, _D]),
+    "idg_beam_taps": (_I, [_P, _I, _P]),
+    "idg_restore": (_I, [_P, _P, _P, _P, _P]),
+    "idg_restore_launch": (_I, [_P, _P, _P, _P, _P, _P]),
 }
 
 
@@ -128,6 +134,21 @@ class CleanParamsStruct(ctypes.Structure):
                 ("gain", ctypes.c_float),
                 ("threshold", ctypes.c_float),
                 ("cycle_fraction", ctypes.c_float)]
+
+
+class BeamStruct(ctypes.Structure):
+    """idg_beam_t (include/idg_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32),
+                ("a", ctypes.c_double), ("b", ctypes.c_double),
+                ("c", ctypes.c_double), ("major", ctypes.c_double),
+                ("minor", ctypes.c_double), ("pa", ctypes.c_double)]
+
+
+class RestoreParamsStruct(ctypes.Structure):
+    """idg_restore_params_t (include/idg_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32),
+                ("grid_size", ctypes.c_int32),
+                ("radius", ctypes.c_int32)]
 
 
 def _load():

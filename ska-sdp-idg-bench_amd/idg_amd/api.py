@@ -12,13 +12,15 @@ Errors: where the reference's C++ entries abort the process (hipCheck ->
 exit, app/HIP/util.cpp:5-15), these raise IdgError carrying the status code
 and message.
 """
+import collections
 import contextlib
 import ctypes
 
 import numpy as np
 
-from ._lib import (CleanParamsStruct, OptionsStruct, PlanParamsStruct,
-                   WeightParamsStruct, lib)
+from ._lib import (BeamStruct, CleanParamsStruct, OptionsStruct,
+                   PlanParamsStruct, RestoreParamsStruct, WeightParamsStruct,
+                   lib)
 
 IMAGE_SIZE = 0.01   # app/common/parameters.hpp:4
 W_STEP = 0.0        # app/common/parameters.hpp:5
@@ -1224,6 +1226,150 @@ def clean(residual, psf, model=None, mask=None, gain=0.1, threshold=0.0,
             if int(state[1:2].cpu()) != 0:
                 break
     return residual, model, components, state
+
+
+# ---------------------------------------------------------------------------
+# Restore (idg_beam_* / idg_restore / idg_restore_launch; not
+# in the reference): model and residual -> the restored image.  The beam and
+# its taps are made on the host; numpy planes take the host entry, torch CUDA
+# tensors the _launch entry (asynchronous); the same bytes either way.
+#   ... -> clean -> beam_fit(psf) -> restore(model, residual, beam=beam)
+# ---------------------------------------------------------------------------
+Beam = collections.namedtuple("Beam", "a b c major minor pa")
+Beam.__doc__ = """The clean beam exp(-(a dx^2 + 2 b dx dy + c dy^2)) (idg_beam_t):
+major >= minor are its FWHMs in pixels, pa the major axis' angle from +x
+towards +y in (-pi/2, pi/2]."""
+
+
+def _beam_struct(beam=None):
+    b = BeamStruct()
+    b.struct_size = ctypes.sizeof(BeamStruct)
+    if beam is not None:
+        b.a, b.b, b.c, b.major, b.minor, b.pa = (float(v) for v in beam)
+    return b, ctypes.cast(ctypes.pointer(b), ctypes.c_void_p)
+
+
+def _beam_of(b):
+    return Beam(b.a, b.b, b.c, b.major, b.minor, b.pa)
+
+
+def beam_from_axes(major, minor, pa=0.0):
+    """The Beam with FWHMs major >= minor > 0 (pixels) and its major axis at
+    angle pa (radians, from +x towards +y)."""
+    b, bp = _beam_struct()
+    _check(lib.idg_beam_from_axes(float(major), float(minor), float(pa), bp),
+           "beam_from_axes")
+    return _beam_of(b)
+
+
+def beam_fit(psf, level=0.5):
+    """The Beam fitted to the main lobe of psf (float32 [Gp, Gp], centre
+    (Gp // 2, Gp // 2)): the pixels at or above level * the centre that are
+    4-connected to it, within 32 pixels (idg_beam_fit; host only, in
+    doubles).  numpy, or a CUDA tensor: then the centre window of at most
+    65 x 65 floats is copied to the host, which synchronises with the current
+    stream."""
+    Gp = _square(psf, "psf")
+    if not isinstance(psf, np.ndarray):
+        import torch
+        _dev_ptr(psf, "psf", torch.float32)
+        # (the window's centre is at (size // 2, size // 2) again: Gp // 2
+        # has as many pixels after it as before it, or one fewer)
+        c = Gp // 2
+        lo, hi = max(c - 32, 0), min(c + 33, Gp)
+        psf = psf[lo:hi, lo:hi].cpu().numpy()
+    psf = np.ascontiguousarray(psf)
+    b, bp = _beam_struct()
+    _check(lib.idg_beam_fit(psf.shape[0], _np_ptr(psf, np.float32, "psf"),
+                            float(level), bp), "beam_fit")
+    return _beam_of(b)
+
+
+def beam_radius(beam, cutoff=1e-6):
+    """The largest integer distance along the major axis at which the beam is
+    still >= cutoff (idg_beam_radius; at most 32)."""
+    b, bp = _beam_struct(beam)
+    r = lib.idg_beam_radius(bp, float(cutoff))
+    if r < 0:
+        raise IdgError(r, "beam_radius")
+    return r
+
+
+def beam_taps(beam, radius=None, cutoff=1e-6):
+    """The beam on the pixels within `radius` (None: beam_radius(beam,
+    cutoff)): float32 [2R + 1, 2R + 1] numpy, the centre 1 (idg_beam_taps)."""
+    if radius is None:
+        radius = beam_radius(beam, cutoff)
+    b, bp = _beam_struct(beam)
+    side = 2 * max(int(radius), 0) + 1
+    taps = np.empty((side, side), np.float32)
+    _check(lib.idg_beam_taps(bp, int(radius), _np_ptr(taps, np.float32,
+                                                      "taps", True)),
+           "beam_taps")
+    return taps
+
+
+def _restore_params(G, R):
+    p = RestoreParamsStruct()
+    p.struct_size = ctypes.sizeof(RestoreParamsStruct)
+    p.grid_size, p.radius = G, R
+    return p, ctypes.cast(ctypes.pointer(p), ctypes.c_void_p)
+
+
+def restore(model, residual=None, taps=None, beam=None, out=None,
+            stream=None):
+    """The restored image (idg_restore / idg_restore_launch): `model`
+    convolved with the clean beam, plus `residual` (None: none).  All planes
+    float32 [G, G].  Give the beam as taps (float32 [2R + 1, 2R + 1], R <= 32,
+    as beam_taps makes them; numpy for numpy planes, a CUDA tensor for CUDA
+    planes) or as beam= (a Beam: its taps at the default cutoff are built on
+    the host and, for CUDA planes, uploaded on `stream`).  out: the plane to
+    write, None for a new one; it may be `residual` itself, and no other
+    overlap of the buffers is allowed.  Only the non-zero model pixels cost
+    anything beyond one pass over the planes.  Returns out."""
+    host = isinstance(model, np.ndarray)
+    G = _square(model, "model")
+    if (taps is None) == (beam is None):
+        raise ValueError("give one of taps and beam")
+    if beam is not None:
+        taps = beam_taps(beam)
+        if not host:
+            import torch
+            with _on_stream(stream):
+                taps = torch.from_numpy(taps).to(model.device,
+                                                 non_blocking=True)
+    side = _square(taps, "taps")
+    if side % 2 != 1:
+        raise ValueError("taps must be [2R + 1, 2R + 1]")
+    R = side // 2
+    if residual is not None and tuple(residual.shape) != (G, G):
+        raise ValueError("residual must be [G][G]")
+    if out is not None and tuple(out.shape) != (G, G):
+        raise ValueError("out must be [G][G]")
+    p, pp = _restore_params(G, R)
+    if host:
+        if out is None:
+            out = np.empty((G, G), np.float32)
+        _check(lib.idg_restore(
+            pp, _np_ptr(model, np.float32, "model"),
+            None if residual is None else _np_ptr(residual, np.float32,
+                                                  "residual"),
+            _np_ptr(taps, np.float32, "taps"),
+            _np_ptr(out, np.float32, "out", True)), "restore")
+        return out
+    import torch
+    if out is None:
+        with _on_stream(stream):
+            out = torch.empty((G, G), dtype=torch.float32,
+                              device=model.device)
+    _check(lib.idg_restore_launch(
+        pp, _dev_ptr(model, "model", torch.float32),
+        None if residual is None else _dev_ptr(residual, "residual",
+                                               torch.float32),
+        _dev_ptr(taps, "taps", torch.float32),
+        _dev_ptr(out, "out", torch.float32), _stream_handle(stream)),
+        "restore")
+    return out
 
 
 # ---------------------------------------------------------------------------
