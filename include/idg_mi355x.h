@@ -803,6 +803,141 @@ int idg_restore_launch(const idg_restore_params_t *params, const float *model,
                        const float *residual, const float *taps,
                        float *restored, void *stream);
 
+/* ---- multi-scale CLEAN -----------------------------------------
+ * The minor cycle of idg_clean over Ns scale-convolved residual planes
+ * (Cornwell 2008): a component is a Gaussian blob of one of Ns widths, found
+ * as the peak over all planes and subtracted from every plane with the
+ * cross-PSF of its scale and the plane's.  No reference counterpart.  Three
+ * layers, each with a host form (host pointers, no device needed) and a
+ * _launch form (device pointers, asynchronous on `stream`, nothing read back,
+ * no synchronisation, scratch from the workspace cache only); both forms
+ * produce the same bytes in every output.  Every float operation is one
+ * rounded float32 operation; fmaf is fused.
+ *
+ * Scales.  A scale a >= 0 is a width in pixels.  a = 0 is the delta: radius
+ * 0, taps {1.0f}.  a > 0: sigma = a * 3 / 16, r = ceil(3 sigma) <= 48, and
+ *   h[k + r] = (float)(exp(-k^2 / (2 sigma^2)) / sum_j exp(-j^2 / (2 sigma^2)))
+ * in doubles, the sum over j = -r ... r in ascending order; the 2-D kernel is
+ * the outer product.  idg_ms_scale_radius returns r, or
+ * IDG_E_INVALID_ARGUMENT for a negative or NaN scale or r > 48;
+ * idg_ms_scale_taps writes the 2 r + 1 taps for radius = that r (host only).
+ * Like the restore taps, the tables are inputs of everything below.
+ *
+ * Convolution.  in, tmp, out: float32 [G][G], 1 <= G <= 16384; taps: float32
+ * [2 r + 1], 0 <= r <= 48.  The image is zero beyond its edge:
+ *   row pass:    tmp[y][x] = acc, acc = +0.0f; for k = -r ... r ascending with
+ *                0 <= x + k < G:  acc = fmaf(in[y][x + k], taps[k + r], acc)
+ *   column pass: out[y][x] = acc, acc = +0.0f; for k = -r ... r ascending with
+ *                0 <= y + k < G:  acc = fmaf(tmp[y + k][x], taps[k + r], acc)
+ * No zero is skipped; NaN and +-inf go in as they are (with taps {1} the
+ * output is the input except that -0 becomes +0).  out may be in; tmp must be
+ * distinct from both; any other overlap is IDG_E_INVALID_ARGUMENT, as are a
+ * NULL buffer and a size out of range.
+ *
+ * Prepare.  idg_ms_params_t: G, Gp (1 <= Gp <= G), 1 <= Ns <= 8 and
+ * radius[s]; radius[0] must be 0 (scale 0 is the delta).  taps: every scale's
+ * taps one after the other, scale s at offset sum_{j < s} (2 radius[j] + 1).
+ * residual [G][G], psf [Gp][Gp] (centre (Gp / 2, Gp / 2)), tmp [G][G];
+ * planes [Ns][G][G]; cross_psf [Ns (Ns + 1) / 2][Gp][Gp], the patch of
+ * (s, q), s <= q, at index s Ns - s (s - 1) / 2 + (q - s).
+ *   planes[0] = residual, a copy (planes may be residual itself);
+ *   planes[s] = convolve(residual, h_s), s >= 1;
+ *   cross(s, q) = convolve(convolve(psf, h_s), h_q) on the [Gp][Gp] window:
+ *   the PSF is zero outside it and the result is truncated to it; each is a
+ *   full row-then-column convolution as above.  cross(q, s) is cross(s, q).
+ * The other fields of the struct are not read.
+ *
+ * Minor cycle.  planes, cross_psf and taps as prepare leaves them; mask uint8
+ * [G][G] or NULL, limiting the search on every scale and never the
+ * subtraction; model float32 [G][G], accumulated onto; components
+ * [max_components]; state: input and output, zeroed by the caller before the
+ * first call: k calls of n iterations give the bytes of one call of k * n.
+ * weight[s] and inv_peak[s] are the caller's: the usual choice is inv_peak[s]
+ * = 1 / cross(s, s)[centre] and weight[s] = (1 - bias a_s / a_max)
+ * inv_peak[s].
+ * Peak: over every scale s and every searchable pixel whose planes[s] value
+ * v is not NaN, the largest u = |weight[s] * v| (one rounded multiply; a NaN
+ * u is excluded too); ties go to the lowest scale, then the lowest linear
+ * index.  One iteration: steps 1 to 5 of idg_clean with u in place of |v|,
+ * then for the peak (py, px) of scale s, value v:
+ *   6. c = (gain * v) * inv_peak[s] (two rounded multiplies);
+ *      components[n_components++] = {py, px, s, c}.
+ *   7. every (y, x) inside the image with |y - py| <= r and |x - px| <= r, r
+ *      = radius[s], h = scale s's taps:
+ *      model[y][x] += (c * h[y - py + r]) * h[x - px + r]   (one add)
+ *   8. every scale q and every (y, x) of idg_clean's step 7:
+ *      planes[q][y][x] = fmaf(-c, cross(s, q)[dy][dx], planes[q][y][x]).
+ * After the call state.peak = u, peak_index and peak_scale describe the planes
+ * as they stand (0, -1, -1 if there is no peak).  The residual to hand on is
+ * planes[0].
+ *
+ * IDG_E_INVALID_ARGUMENT (every buffer left as it was): idg_clean's list, Ns
+ * outside [1, 8], a radius outside [0, 48] or radius[0] != 0, a weight or
+ * inv_peak of a used scale that is not finite, and (host form) a state with
+ * n_components outside [0, max_components]; on such a state the _launch form
+ * runs no iteration. */
+#define IDG_MS_MAX_SCALES 8
+#define IDG_MS_MAX_RADIUS 48
+
+typedef struct idg_ms_params_t {
+  uint32_t struct_size; /* sizeof(idg_ms_params_t)                           */
+  int32_t grid_size;    /* G                                                 */
+  int32_t psf_size;     /* Gp                                                */
+  int32_t max_components;
+  int32_t nr_iterations;
+  float gain;
+  float threshold;
+  float cycle_fraction;
+  int32_t nr_scales;    /* Ns                                                */
+  int32_t radius[IDG_MS_MAX_SCALES];
+  float weight[IDG_MS_MAX_SCALES];
+  float inv_peak[IDG_MS_MAX_SCALES];
+} idg_ms_params_t;
+
+typedef struct idg_ms_component_t {
+  int32_t y, x, scale;
+  float value;
+} idg_ms_component_t;
+
+typedef struct idg_ms_state_t {
+  int32_t n_components;
+  int32_t reason;     /* IDG_CLEAN_*                                         */
+  int32_t started;
+  int32_t peak_index; /* y * G + x of the peak, -1: none                     */
+  float level;
+  float peak;         /* |weight[peak_scale] * v| there                      */
+  int32_t peak_scale; /* -1: none                                            */
+} idg_ms_state_t;
+
+/* >= 0: the radius. */
+int idg_ms_scale_radius(double scale);
+int idg_ms_scale_taps(double scale, int radius, float *taps);
+
+int idg_convolve_separable(int grid_size, int radius, const float *in,
+                           const float *taps, float *tmp, float *out);
+/* Two launches, nothing allocated. */
+int idg_convolve_separable_launch(int grid_size, int radius, const float *in,
+                                  const float *taps, float *tmp, float *out,
+                                  void *stream);
+
+int idg_ms_prepare(const idg_ms_params_t *params, const float *residual,
+                   const float *psf, const float *taps, float *planes,
+                   float *cross_psf, float *tmp);
+int idg_ms_prepare_launch(const idg_ms_params_t *params, const float *residual,
+                          const float *psf, const float *taps, float *planes,
+                          float *cross_psf, float *tmp, void *stream);
+
+int idg_ms_clean(const idg_ms_params_t *params, float *planes,
+                 const float *cross_psf, const float *taps,
+                 const uint8_t *mask, float *model,
+                 idg_ms_component_t *components, idg_ms_state_t *state);
+/* One launch per iteration plus two, as idg_clean_launch. */
+int idg_ms_clean_launch(const idg_ms_params_t *params, float *planes,
+                        const float *cross_psf, const float *taps,
+                        const uint8_t *mask, float *model,
+                        idg_ms_component_t *components, idg_ms_state_t *state,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -261,6 +261,164 @@ static_assert(IDG_CLEAN_RUNNING == idg_mi355x::clean::kRunning &&
                   sizeof(idg_clean_state_t) == 24,
               "idg_clean_* records are clean:: records");
 
+// Half-open byte ranges of a call's buffers: `who`: "a and b overlap" for the
+// first pair that does and is not listed in `may` (pairs of indices that may
+// be the same pointer).  Null buffers are skipped.
+struct Span {
+  const char *name;
+  const void *at;
+  size_t bytes;
+};
+int no_overlap(const char *who, const std::vector<Span> &spans,
+               const std::vector<std::pair<int, int>> &may = {}) {
+  for (size_t i = 0; i < spans.size(); ++i)
+    for (size_t j = i + 1; j < spans.size(); ++j) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(spans[i].at);
+      const uintptr_t b = reinterpret_cast<uintptr_t>(spans[j].at);
+      if (a == 0 || b == 0) continue;
+      bool allowed = false;
+      for (const auto &m : may)
+        allowed |= m.first == static_cast<int>(i) &&
+                   m.second == static_cast<int>(j) && a == b;
+      if (allowed) continue;
+      if (a < b + spans[j].bytes && b < a + spans[i].bytes)
+        return fail(IDG_E_INVALID_ARGUMENT,
+                    std::string(who) + ": " + spans[i].name + " and " +
+                        spans[j].name + " overlap");
+    }
+  return IDG_OK;
+}
+
+// The sizes and buffers of a convolution call (`entry`: which of the two).
+int parse_convolve(const char *entry, int grid_size, int radius,
+                   const float *in, const float *taps, const float *tmp,
+                   const float *out) {
+  namespace ms = idg_mi355x::ms;
+  if (grid_size < 1 || grid_size > ms::kMaxGridSize || radius < 0 ||
+      radius > ms::kMaxRadius)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                std::string(entry) + ": 1 <= grid_size <= 16384 and 0 <= "
+                                     "radius <= 48 required");
+  if (!in || !taps || !tmp || !out)
+    return fail(IDG_E_INVALID_ARGUMENT, std::string(entry) + ": null buffer");
+  const size_t plane = sizeof(float) * grid_size * grid_size;
+  return no_overlap(entry,
+                    {{"in", in, plane},
+                     {"out", out, plane},
+                     {"tmp", tmp, plane},
+                     {"taps", taps, sizeof(float) * (2 * radius + 1)}},
+                    {{0, 1}});
+}
+
+// idg_ms_params_t (read_struct) -> ms::Params.  minor_cycle: the fields only
+// idg_ms_clean reads are checked too.
+int parse_ms(const idg_ms_params_t *params, bool minor_cycle,
+             idg_mi355x::ms::Params *out) {
+  namespace ms = idg_mi355x::ms;
+  idg_ms_params_t v;
+  if (int rc = read_struct(params, "idg_ms_params_t", &v)) return rc;
+  if (v.psf_size < 1 || v.grid_size < v.psf_size ||
+      v.grid_size > ms::kMaxGridSize)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "multiscale: 1 <= psf_size <= grid_size <= 16384 required");
+  if (v.nr_scales < 1 || v.nr_scales > ms::kMaxScales)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "multiscale: 1 <= nr_scales <= 8 required");
+  if (v.radius[0] != 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "multiscale: radius[0] must be 0 (scale 0 is the delta)");
+  for (int s = 0; s < v.nr_scales; ++s)
+    if (v.radius[s] < 0 || v.radius[s] > ms::kMaxRadius)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "multiscale: 0 <= radius <= 48 required");
+  if (minor_cycle) {
+    if (!std::isfinite(v.gain) || !std::isfinite(v.threshold) ||
+        !std::isfinite(v.cycle_fraction) || v.threshold < 0.0f ||
+        v.cycle_fraction < 0.0f)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "multiscale: gain, threshold and cycle_fraction must be "
+                  "finite, threshold and cycle_fraction not negative");
+    if (v.nr_iterations < 0 || v.max_components < 0)
+      return fail(IDG_E_INVALID_ARGUMENT,
+                  "multiscale: nr_iterations >= 0 and max_components >= 0 "
+                  "required");
+    for (int s = 0; s < v.nr_scales; ++s)
+      if (!std::isfinite(v.weight[s]) || !std::isfinite(v.inv_peak[s]))
+        return fail(IDG_E_INVALID_ARGUMENT,
+                    "multiscale: weight and inv_peak must be finite");
+  }
+  *out = ms::Params();
+  out->base.grid_size = v.grid_size;
+  out->base.psf_size = v.psf_size;
+  out->base.max_components = v.max_components;
+  out->base.nr_iterations = v.nr_iterations;
+  out->base.gain = v.gain;
+  out->base.threshold = v.threshold;
+  out->base.cycle_fraction = v.cycle_fraction;
+  out->nr_scales = v.nr_scales;
+  for (int s = 0; s < v.nr_scales; ++s) {
+    out->radius[s] = v.radius[s];
+    out->weight[s] = v.weight[s];
+    out->inv_peak[s] = v.inv_peak[s];
+  }
+  return IDG_OK;
+}
+static_assert(IDG_MS_MAX_SCALES == idg_mi355x::ms::kMaxScales &&
+                  IDG_MS_MAX_RADIUS == idg_mi355x::ms::kMaxRadius &&
+                  sizeof(idg_ms_component_t) ==
+                      sizeof(idg_mi355x::ms::Component) &&
+                  sizeof(idg_ms_component_t) == 16 &&
+                  sizeof(idg_ms_state_t) == sizeof(idg_mi355x::ms::State) &&
+                  sizeof(idg_ms_state_t) == 28,
+              "idg_ms_* records are ms:: records");
+
+// The buffers of a prepare call and of a minor-cycle call (`entry`: which
+// form): none null but the mask, none overlapping.
+int ms_prepare_buffers(const char *entry, const idg_mi355x::ms::Params &p,
+                       const float *residual, const float *psf,
+                       const float *taps, const float *planes,
+                       const float *cross_psf, const float *tmp) {
+  namespace ms = idg_mi355x::ms;
+  if (!residual || !psf || !taps || !planes || !cross_psf || !tmp)
+    return fail(IDG_E_INVALID_ARGUMENT, std::string(entry) + ": null buffer");
+  const size_t plane = sizeof(float) * p.base.grid_size * p.base.grid_size;
+  const size_t patch = sizeof(float) * p.base.psf_size * p.base.psf_size;
+  const int Ns = p.nr_scales;
+  // (residual may be planes[0] itself: the same pointer)
+  return no_overlap(
+      entry,
+      {{"residual", residual, plane},
+       {"planes", planes, plane * Ns},
+       {"psf", psf, patch},
+       {"taps", taps, sizeof(float) * ms::taps_at(p, Ns)},
+       {"cross_psf", cross_psf, patch * (Ns * (Ns + 1) / 2)},
+       {"tmp", tmp, plane}},
+      {{0, 1}});
+}
+int ms_clean_buffers(const char *entry, const idg_mi355x::ms::Params &p,
+                     const float *planes, const float *cross_psf,
+                     const float *taps, const uint8_t *mask,
+                     const float *model, const void *components,
+                     const void *state) {
+  namespace ms = idg_mi355x::ms;
+  if (!planes || !cross_psf || !taps || !model || !components || !state)
+    return fail(IDG_E_INVALID_ARGUMENT, std::string(entry) + ": null buffer");
+  const size_t cells =
+      static_cast<size_t>(p.base.grid_size) * p.base.grid_size;
+  const size_t patch = sizeof(float) * p.base.psf_size * p.base.psf_size;
+  const int Ns = p.nr_scales;
+  return no_overlap(
+      entry,
+      {{"planes", planes, sizeof(float) * cells * Ns},
+       {"cross_psf", cross_psf, patch * (Ns * (Ns + 1) / 2)},
+       {"taps", taps, sizeof(float) * ms::taps_at(p, Ns)},
+       {"mask", mask, cells},
+       {"model", model, sizeof(float) * cells},
+       {"components", components,
+        sizeof(idg_ms_component_t) * p.base.max_components},
+       {"state", state, sizeof(idg_ms_state_t)}});
+}
+
 // idg_beam_t (read_struct) -> host::Beam; `who`: the entry.  The form must be
 // positive definite.
 int parse_beam(const idg_beam_t *beam, const char *who,
@@ -1084,6 +1242,107 @@ int idg_restore_launch(const idg_restore_params_t *params, const float *model,
                                              restored,
                                              static_cast<hipStream_t>(stream)),
                   "idg_restore_launch");
+}
+
+int idg_ms_scale_radius(double scale) {
+  const int r = idg_mi355x::host::ms_scale_radius(scale);
+  if (r < 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_ms_scale_radius: scale >= 0 with ceil(9 scale / 16) <= "
+                "48 required");
+  return r;
+}
+
+int idg_ms_scale_taps(double scale, int radius, float *taps) {
+  const int r = idg_mi355x::host::ms_scale_radius(scale);
+  if (r < 0 || r != radius)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "idg_ms_scale_taps: radius must be idg_ms_scale_radius(scale)");
+  if (taps == nullptr)
+    return fail(IDG_E_INVALID_ARGUMENT, "idg_ms_scale_taps: null buffer");
+  idg_mi355x::host::ms_scale_taps(scale, radius, taps);
+  return IDG_OK;
+}
+
+int idg_convolve_separable(int grid_size, int radius, const float *in,
+                           const float *taps, float *tmp, float *out) {
+  if (int rc = parse_convolve("idg_convolve_separable", grid_size, radius, in,
+                              taps, tmp, out))
+    return rc;
+  idg_mi355x::host::convolve_separable(grid_size, radius, in, taps, tmp, out);
+  return IDG_OK;
+}
+
+int idg_convolve_separable_launch(int grid_size, int radius, const float *in,
+                                  const float *taps, float *tmp, float *out,
+                                  void *stream) {
+  if (int rc = parse_convolve("idg_convolve_separable_launch", grid_size,
+                              radius, in, taps, tmp, out))
+    return rc;
+  return from_hip(idg_mi355x::launch_convolve_separable(
+                      grid_size, radius, in, taps, tmp, out,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_convolve_separable_launch");
+}
+
+int idg_ms_prepare(const idg_ms_params_t *params, const float *residual,
+                   const float *psf, const float *taps, float *planes,
+                   float *cross_psf, float *tmp) {
+  idg_mi355x::ms::Params p;
+  if (int rc = parse_ms(params, false, &p)) return rc;
+  if (int rc = ms_prepare_buffers("idg_ms_prepare", p, residual, psf, taps,
+                                  planes, cross_psf, tmp))
+    return rc;
+  idg_mi355x::host::ms_prepare(p, residual, psf, taps, planes, cross_psf, tmp);
+  return IDG_OK;
+}
+
+int idg_ms_prepare_launch(const idg_ms_params_t *params, const float *residual,
+                          const float *psf, const float *taps, float *planes,
+                          float *cross_psf, float *tmp, void *stream) {
+  idg_mi355x::ms::Params p;
+  if (int rc = parse_ms(params, false, &p)) return rc;
+  if (int rc = ms_prepare_buffers("idg_ms_prepare_launch", p, residual, psf,
+                                  taps, planes, cross_psf, tmp))
+    return rc;
+  return from_hip(idg_mi355x::launch_ms_prepare(
+                      p, residual, psf, taps, planes, cross_psf, tmp,
+                      static_cast<hipStream_t>(stream)),
+                  "idg_ms_prepare_launch");
+}
+
+int idg_ms_clean(const idg_ms_params_t *params, float *planes,
+                 const float *cross_psf, const float *taps,
+                 const uint8_t *mask, float *model,
+                 idg_ms_component_t *components, idg_ms_state_t *state) {
+  namespace ms = idg_mi355x::ms;
+  ms::Params p;
+  if (int rc = parse_ms(params, true, &p)) return rc;
+  if (int rc = ms_clean_buffers("idg_ms_clean", p, planes, cross_psf, taps,
+                                mask, model, components, state))
+    return rc;
+  const std::string msg = idg_mi355x::host::ms_clean(
+      p, planes, cross_psf, taps, mask, model,
+      reinterpret_cast<ms::Component *>(components),
+      reinterpret_cast<ms::State *>(state));
+  if (!msg.empty()) return fail(IDG_E_INVALID_ARGUMENT, msg);
+  return IDG_OK;
+}
+
+int idg_ms_clean_launch(const idg_ms_params_t *params, float *planes,
+                        const float *cross_psf, const float *taps,
+                        const uint8_t *mask, float *model,
+                        idg_ms_component_t *components, idg_ms_state_t *state,
+                        void *stream) {
+  idg_mi355x::ms::Params p;
+  if (int rc = parse_ms(params, true, &p)) return rc;
+  if (int rc = ms_clean_buffers("idg_ms_clean_launch", p, planes, cross_psf,
+                                taps, mask, model, components, state))
+    return rc;
+  return from_hip(idg_mi355x::launch_ms_clean(
+                      p, planes, cross_psf, taps, mask, model, components,
+                      state, static_cast<hipStream_t>(stream)),
+                  "idg_ms_clean_launch");
 }
 
 double idg_p_run_gridder(void) {

@@ -189,7 +189,8 @@ hipError_t launch_parts(const KernelChoice &k, int nr_subgrids, void **args13,
 // (never clean) freed after the sequence.
 constexpr int kWorkspaceQueue = 0, kWorkspaceHomeSort = 1,
               kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3, kWorkspacePlan = 4,
-              kWorkspaceWeight = 5, kWorkspaceClean = 6;
+              kWorkspaceWeight = 5, kWorkspaceClean = 6,
+              kWorkspaceMultiscale = 7;
 // Not copyable: a copy would release the slot twice.
 struct WorkspaceLease {
   void *ptr = nullptr;
@@ -369,6 +370,35 @@ hipError_t launch_clean(const clean::Params &params, float *d_residual,
                         const float *d_psf, const uint8_t *d_mask,
                         float *d_model, void *d_components, void *d_state,
                         hipStream_t stream);
+
+// Multi-scale CLEAN on the device (kernels/multiscale_mi355x.hip.cpp; DESIGN.md
+// §17), bit for bit the host entries of common/multiscale.hpp's arithmetic.
+// launch_convolve_separable: the row pass into d_tmp and the column pass into
+// d_out (which may be d_in), two launches, no workspace.  launch_ms_prepare:
+// the scale planes and the cross-PSFs, launches of those two passes and one
+// device-to-device copy.  launch_ms_clean: one search launch,
+// params.base.nr_iterations iteration launches and one finish launch,
+// continuing from *d_state (ms::State) and leaving it there; the tiles'
+// partials and the double-buffered state live on a kWorkspaceMultiscale
+// lease.  Nothing is read back.  d_taps: every scale's taps, one after the
+// other; d_mask may be null; d_components: ms::Component
+// [params.base.max_components].
+namespace ms {
+struct Params;
+}
+hipError_t launch_convolve_separable(int grid_size, int radius,
+                                     const float *d_in, const float *d_taps,
+                                     float *d_tmp, float *d_out,
+                                     hipStream_t stream);
+hipError_t launch_ms_prepare(const ms::Params &params, const float *d_residual,
+                             const float *d_psf, const float *d_taps,
+                             float *d_planes, float *d_cross_psf, float *d_tmp,
+                             hipStream_t stream);
+hipError_t launch_ms_clean(const ms::Params &params, float *d_planes,
+                           const float *d_cross_psf, const float *d_taps,
+                           const uint8_t *d_mask, float *d_model,
+                           void *d_components, void *d_state,
+                           hipStream_t stream);
 
 // The restore step on the device (kernels/restore_mi355x.hip.cpp; DESIGN.md
 // §16), bit for bit the host entry of common/restore.hpp's arithmetic: one

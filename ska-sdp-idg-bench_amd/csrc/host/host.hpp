@@ -1,7 +1,7 @@
 // host.hpp -- the host twins of the device steps: the plan walk, the imaging
-// weights, the Hogbom minor cycle, the restore step and the taper's image.
-// Plain C++ over the per-element rules of
-// common/{plan,weight,clean,restore}.hpp, no HIP call, so they
+// weights, the Hogbom minor cycle, multi-scale CLEAN, the restore step and the
+// taper's image.  Plain C++ over the per-element rules of
+// common/{plan,weight,clean,multiscale,restore}.hpp, no HIP call, so they
 // run (and compile) without a GPU; the GPU suites compare the device kernels
 // against them bit for bit.  Each takes the parsed values its launch_*
 // counterpart (hip/util.hpp) takes; the C ABI (capi/idg_capi.cpp) validates
@@ -14,6 +14,7 @@
 #include <string>
 
 #include "common/clean.hpp"
+#include "common/multiscale.hpp"
 #include "common/plan.hpp"
 #include "common/restore.hpp"
 #include "common/types.hpp"
@@ -92,6 +93,27 @@ void beam_taps(const Beam &beam, int radius, float *taps);
 std::string restore(const restore::Params &params, const float *model,
                     const float *residual, const float *taps,
                     float *restored);
+
+// host/multiscale.cpp.  A scale's Gaussian in doubles: its
+// radius ceil(3 sigma), sigma = scale * 3 / 16 (-1: scale negative, NaN or
+// wider than ms::kMaxRadius), and its 2 radius + 1 normalised taps.
+int ms_scale_radius(double scale);
+void ms_scale_taps(double scale, int radius, float *taps);
+// The dense separable convolution of a [G][G] plane that is zero beyond its
+// edge: the row pass into tmp, the column pass into out (which may be `in`).
+void convolve_separable(int grid_size, int radius, const float *in,
+                        const float *taps, float *tmp, float *out);
+// planes[Ns][G][G] and cross_psf[Ns (Ns + 1) / 2][Gp][Gp] from the residual
+// and the PSF; taps: every scale's, one after the other; tmp[G][G].
+void ms_prepare(const ms::Params &params, const float *residual,
+                const float *psf, const float *taps, float *planes,
+                float *cross_psf, float *tmp);
+// params.base.nr_iterations iterations from *state; mask may be null.  Not
+// empty: the state no iteration may run from, every buffer left as it was.
+std::string ms_clean(const ms::Params &params, float *planes,
+                     const float *cross_psf, const float *taps,
+                     const uint8_t *mask, float *model,
+                     ms::Component *components, ms::State *state);
 
 // host/image.cpp.  out[G][G]: the [S][S] taper interpolated
 // to the image's pixels, in doubles.

@@ -22,9 +22,13 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   CLEAN_REASONS, COMPONENT_DTYPE, STATE_DTYPE, clean,
                   model_image, stokes_i,
                   Beam, beam_fit, beam_from_axes, beam_radius, beam_taps,
-                  restore)
-from ._lib import (LIB_PATH, BeamStruct, CleanParamsStruct, OptionsStruct,
-                   PlanParamsStruct, RestoreParamsStruct, WeightParamsStruct)
+                  restore,
+                  MS_COMPONENT_DTYPE, MS_STATE_DTYPE, clean_multiscale,
+                  convolve_separable, ms_clean, ms_prepare, ms_scale_taps,
+                  ms_weights)
+from ._lib import (LIB_PATH, BeamStruct, CleanParamsStruct, MsParamsStruct,
+                   OptionsStruct, PlanParamsStruct, RestoreParamsStruct,
+                   WeightParamsStruct)
 from . import shard
 
 __all__ = [
@@ -46,4 +50,7 @@ __all__ = [
     "stokes_i", "CleanParamsStruct",
     "Beam", "beam_fit", "beam_from_axes", "beam_radius", "beam_taps",
     "restore", "BeamStruct", "RestoreParamsStruct",
+    "MS_COMPONENT_DTYPE", "MS_STATE_DTYPE", "clean_multiscale",
+    "convolve_separable", "ms_clean", "ms_prepare", "ms_scale_taps",
+    "ms_weights", "MsParamsStruct",
 ]

@@ -90,6 +90,14 @@ SIGNATURES = {
     "idg_beam_taps": (_I, [_P, _I, _P]),
     "idg_restore": (_I, [_P, _P, _P, _P, _P]),
     "idg_restore_launch": (_I, [_P, _P, _P, _P, _P, _P]),
+    "idg_ms_scale_radius": (_I, [_D]),
+    "idg_ms_scale_taps": (_I, [_D, _I, _P]),
+    "idg_convolve_separable": (_I, [_I, _I, _P, _P, _P, _P]),
+    "idg_convolve_separable_launch": (_I, [_I, _I, _P, _P, _P, _P, _P]),
+    "idg_ms_prepare": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "idg_ms_prepare_launch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "idg_ms_clean": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "idg_ms_clean_launch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 
@@ -134,6 +142,22 @@ class CleanParamsStruct(ctypes.Structure):
                 ("gain", ctypes.c_float),
                 ("threshold", ctypes.c_float),
                 ("cycle_fraction", ctypes.c_float)]
+
+
+class MsParamsStruct(ctypes.Structure):
+    """idg_ms_params_t (include/idg_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32),
+                ("grid_size", ctypes.c_int32),
+                ("psf_size", ctypes.c_int32),
+                ("max_components", ctypes.c_int32),
+                ("nr_iterations", ctypes.c_int32),
+                ("gain", ctypes.c_float),
+                ("threshold", ctypes.c_float),
+                ("cycle_fraction", ctypes.c_float),
+                ("nr_scales", ctypes.c_int32),
+                ("radius", ctypes.c_int32 * 8),
+                ("weight", ctypes.c_float * 8),
+                ("inv_peak", ctypes.c_float * 8)]
 
 
 class BeamStruct(ctypes.Structure):

@@ -18,9 +18,9 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (BeamStruct, CleanParamsStruct, OptionsStruct,
-                   PlanParamsStruct, RestoreParamsStruct, WeightParamsStruct,
-                   lib)
+from ._lib import (BeamStruct, CleanParamsStruct, MsParamsStruct,
+                   OptionsStruct, PlanParamsStruct, RestoreParamsStruct,
+                   WeightParamsStruct, lib)
 
 IMAGE_SIZE = 0.01   # app/common/parameters.hpp:4
 W_STEP = 0.0        # app/common/parameters.hpp:5
@@ -1226,6 +1226,342 @@ def clean(residual, psf, model=None, mask=None, gain=0.1, threshold=0.0,
             if int(state[1:2].cpu()) != 0:
                 break
     return residual, model, components, state
+
+
+# ---------------------------------------------------------------------------
+# Multi-scale CLEAN (idg_ms_* / idg_convolve_separable; not in
+# the reference).  numpy planes take the host entries, torch CUDA tensors the
+# _launch entries (asynchronous); the same bytes either way.
+#   ... -> clean_multiscale(residual, psf) -> restore(model, residual, ...)
+# ---------------------------------------------------------------------------
+MS_COMPONENT_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4"), ("scale", "<i4"),
+                               ("value", "<f4")])
+MS_STATE_DTYPE = np.dtype(STATE_DTYPE.descr + [("peak_scale", "<i4")])
+assert MS_COMPONENT_DTYPE.itemsize == 16 and MS_STATE_DTYPE.itemsize == 28
+MS_MAX_SCALES = 8
+
+
+def ms_scale_taps(scales):
+    """The 1-D taps of every scale (idg_ms_scale_radius / idg_ms_scale_taps;
+    host only, in doubles): a list of float32 arrays [2 r + 1], r = ceil(3
+    sigma), sigma = scale * 3 / 16; scale 0 gives [1.0].  The 2-D kernel of a
+    scale is the outer product of its taps with themselves."""
+    out = []
+    for a in scales:
+        r = lib.idg_ms_scale_radius(float(a))
+        if r < 0:
+            raise IdgError(r, "ms_scale_taps")
+        taps = np.empty(2 * r + 1, np.float32)
+        _check(lib.idg_ms_scale_taps(float(a), r,
+                                     _np_ptr(taps, np.float32, "taps", True)),
+               "ms_scale_taps")
+        out.append(taps)
+    return out
+
+
+def _ms_taps(taps):
+    """A list of per-scale tap arrays -> (radii, the concatenated table)."""
+    taps = [np.ascontiguousarray(t, np.float32).reshape(-1) for t in taps]
+    if not 1 <= len(taps) <= MS_MAX_SCALES:
+        raise ValueError("1 to 8 scales")
+    if any(t.size % 2 != 1 for t in taps):
+        raise ValueError("a scale's taps must be [2 r + 1]")
+    return [t.size // 2 for t in taps], np.concatenate(taps)
+
+
+def _ms_params(G, Gp, radii, max_components=0, nr_iterations=0, gain=0.0,
+               threshold=0.0, cycle_fraction=0.0, weight=None, inv_peak=None):
+    p = MsParamsStruct()
+    p.struct_size = ctypes.sizeof(MsParamsStruct)
+    p.grid_size, p.psf_size, p.nr_scales = G, Gp, len(radii)
+    p.max_components, p.nr_iterations = max_components, nr_iterations
+    p.gain, p.threshold, p.cycle_fraction = gain, threshold, cycle_fraction
+    for s, r in enumerate(radii):
+        p.radius[s] = r
+        p.weight[s] = 1.0 if weight is None else weight[s]
+        p.inv_peak[s] = 1.0 if inv_peak is None else inv_peak[s]
+    return p, ctypes.cast(ctypes.pointer(p), ctypes.c_void_p)
+
+
+def _to_device(a, like, stream):
+    import torch
+    with _on_stream(stream):
+        return torch.from_numpy(a).to(like.device, non_blocking=True)
+
+
+def convolve_separable(image, taps, out=None, tmp=None, stream=None):
+    """Dense separable convolution (idg_convolve_separable / _launch): `image`
+    float32 [G, G], zero beyond its edge, with the outer product of `taps`
+    (float32 [2 r + 1], r <= 48; numpy, uploaded on `stream` for CUDA planes,
+    or a CUDA tensor): a row pass into `tmp`, a column pass into `out`, every
+    pixel's taps taken in ascending order with one fmaf each.  out: None for a
+    new plane; it may be `image`.  tmp: a [G, G] scratch plane distinct from
+    both, None for a new one.  Returns out."""
+    host = isinstance(image, np.ndarray)
+    G = _square(image, "image")
+    if taps.ndim != 1 or taps.shape[0] % 2 != 1:
+        raise ValueError("taps must be [2 r + 1]")
+    r = taps.shape[0] // 2
+    if host:
+        out = np.empty((G, G), np.float32) if out is None else out
+        tmp = np.empty((G, G), np.float32) if tmp is None else tmp
+        if out.shape != image.shape or tmp.shape != image.shape:
+            raise ValueError("out and tmp must be [G][G]")
+        _check(lib.idg_convolve_separable(
+            G, r, _np_ptr(image, np.float32, "image"),
+            _np_ptr(taps, np.float32, "taps"),
+            _np_ptr(tmp, np.float32, "tmp", True),
+            _np_ptr(out, np.float32, "out", True)), "convolve_separable")
+        return out
+    import torch
+    if isinstance(taps, np.ndarray):
+        taps = _to_device(np.ascontiguousarray(taps, np.float32), image,
+                          stream)
+    with _on_stream(stream):
+        if out is None:
+            out = torch.empty_like(image)
+        if tmp is None:
+            tmp = torch.empty_like(image)
+    if out.shape != image.shape or tmp.shape != image.shape:
+        raise ValueError("out and tmp must be [G][G]")
+    _check(lib.idg_convolve_separable_launch(
+        G, r, _dev_ptr(image, "image", torch.float32),
+        _dev_ptr(taps, "taps", torch.float32),
+        _dev_ptr(tmp, "tmp", torch.float32),
+        _dev_ptr(out, "out", torch.float32), _stream_handle(stream)),
+        "convolve_separable")
+    return out
+
+
+def ms_prepare(residual, psf, taps, planes=None, cross_psf=None, tmp=None,
+               stream=None):
+    """The scale planes and the cross-PSFs (idg_ms_prepare / _launch), once
+    per major cycle.  residual float32 [G, G], psf float32 [Gp, Gp], taps: the
+    list ms_scale_taps makes (the first scale must be 0).  planes [Ns, G, G]:
+    planes[0] a copy of the residual, planes[s] the residual convolved with
+    scale s.  cross_psf [Ns (Ns + 1) / 2, Gp, Gp]: the PSF convolved with
+    scales s and q, s <= q, row-major over the pairs, truncated to the PSF's
+    window.  None: new buffers; tmp: a [G, G] scratch plane.  Returns (planes,
+    cross_psf)."""
+    host = isinstance(residual, np.ndarray)
+    G, Gp = _square(residual, "residual"), _square(psf, "psf")
+    radii, table = _ms_taps(taps)
+    Ns = len(radii)
+    pairs = Ns * (Ns + 1) // 2
+    p, pp = _ms_params(G, Gp, radii)
+    if host:
+        planes = np.empty((Ns, G, G), np.float32) if planes is None else planes
+        if cross_psf is None:
+            cross_psf = np.empty((pairs, Gp, Gp), np.float32)
+        tmp = np.empty((G, G), np.float32) if tmp is None else tmp
+        if (planes.shape != (Ns, G, G) or cross_psf.shape != (pairs, Gp, Gp)
+                or tmp.shape != (G, G)):
+            raise ValueError("planes must be [Ns][G][G], cross_psf "
+                             "[Ns (Ns + 1) / 2][Gp][Gp], tmp [G][G]")
+        _check(lib.idg_ms_prepare(
+            pp, _np_ptr(residual, np.float32, "residual"),
+            _np_ptr(psf, np.float32, "psf"),
+            _np_ptr(table, np.float32, "taps"),
+            _np_ptr(planes, np.float32, "planes", True),
+            _np_ptr(cross_psf, np.float32, "cross_psf", True),
+            _np_ptr(tmp, np.float32, "tmp", True)), "ms_prepare")
+        return planes, cross_psf
+    import torch
+    table = _to_device(table, residual, stream)
+    with _on_stream(stream):
+        kw = dict(dtype=torch.float32, device=residual.device)
+        if planes is None:
+            planes = torch.empty((Ns, G, G), **kw)
+        if cross_psf is None:
+            cross_psf = torch.empty((pairs, Gp, Gp), **kw)
+        if tmp is None:
+            tmp = torch.empty((G, G), **kw)
+    if (tuple(planes.shape) != (Ns, G, G)
+            or tuple(cross_psf.shape) != (pairs, Gp, Gp)
+            or tuple(tmp.shape) != (G, G)):
+        raise ValueError("planes must be [Ns][G][G], cross_psf "
+                         "[Ns (Ns + 1) / 2][Gp][Gp], tmp [G][G]")
+    _check(lib.idg_ms_prepare_launch(
+        pp, _dev_ptr(residual, "residual", torch.float32),
+        _dev_ptr(psf, "psf", torch.float32),
+        _dev_ptr(table, "taps", torch.float32),
+        _dev_ptr(planes, "planes", torch.float32),
+        _dev_ptr(cross_psf, "cross_psf", torch.float32),
+        _dev_ptr(tmp, "tmp", torch.float32), _stream_handle(stream)),
+        "ms_prepare")
+    return planes, cross_psf
+
+
+def ms_clean(planes, cross_psf, taps, weight, inv_peak, model=None, mask=None,
+             gain=0.1, threshold=0.0, cycle_fraction=0.0, max_components=1000,
+             nr_iterations=None, components=None, state=None,
+             check_every=None, stream=None):
+    """The multi-scale minor cycle on prepared planes (idg_ms_clean /
+    _launch), the entry clean_multiscale() is built on.  planes [Ns, G, G] and
+    cross_psf [Ns (Ns + 1) / 2, Gp, Gp], both updated / read as ms_prepare
+    leaves them; taps: ms_scale_taps' list; weight, inv_peak: Ns floats each,
+    what a plane's values are multiplied by for the search and a component's
+    value for its flux.  model, mask, components, state, nr_iterations,
+    check_every as for clean(); numpy: MS_COMPONENT_DTYPE and MS_STATE_DTYPE
+    records; torch: int32 [max_components, 4] and int32 [7].  Returns (planes,
+    model, components, state)."""
+    host = isinstance(planes, np.ndarray)
+    if planes.ndim != 3 or cross_psf.ndim != 3:
+        raise ValueError("planes must be [Ns][G][G], cross_psf "
+                         "[Ns (Ns + 1) / 2][Gp][Gp]")
+    radii, table = _ms_taps(taps)
+    Ns = len(radii)
+    G, Gp = _square(planes[0], "planes"), _square(cross_psf[0], "cross_psf")
+    if (planes.shape[0] != Ns or cross_psf.shape[0] != Ns * (Ns + 1) // 2
+            or len(weight) != Ns or len(inv_peak) != Ns):
+        raise ValueError("planes, cross_psf, weight and inv_peak must match "
+                         "the number of scales")
+    if nr_iterations is None:
+        nr_iterations = max_components
+    records = max(max_components, 1)     # (never a null pointer)
+
+    def params(n):
+        return _ms_params(G, Gp, radii, max_components, n, gain, threshold,
+                          cycle_fraction, weight, inv_peak)
+    if host:
+        if model is None:
+            model = np.zeros((G, G), np.float32)
+        if components is None:
+            components = np.zeros(records, MS_COMPONENT_DTYPE)
+        if state is None:
+            state = np.zeros(1, MS_STATE_DTYPE)
+        if (model.shape != (G, G) or components.size < max_components
+                or state.size != 1
+                or (mask is not None and mask.shape != (G, G))):
+            raise ValueError("model and mask must be [G][G], components "
+                             "[max_components], state [1]")
+        if mask is not None and mask.dtype == np.bool_:
+            mask = mask.view(np.uint8)
+        p, pp = params(nr_iterations)
+        _check(lib.idg_ms_clean(
+            pp, _np_ptr(planes, np.float32, "planes", True),
+            _np_ptr(cross_psf, np.float32, "cross_psf"),
+            _np_ptr(table, np.float32, "taps"),
+            None if mask is None else _np_ptr(mask, np.uint8, "mask"),
+            _np_ptr(model, np.float32, "model", True),
+            _np_ptr(components, MS_COMPONENT_DTYPE, "components", True),
+            _np_ptr(state, MS_STATE_DTYPE, "state", True)), "ms_clean")
+        return planes, model, components, state
+    import torch
+    dev = planes.device
+    table = _to_device(table, planes, stream)
+    with _on_stream(stream):
+        if model is None:
+            model = torch.zeros((G, G), dtype=torch.float32, device=dev)
+        if components is None:
+            components = torch.zeros((records, 4), dtype=torch.int32,
+                                     device=dev)
+        if state is None:
+            state = torch.zeros(7, dtype=torch.int32, device=dev)
+    if (tuple(model.shape) != (G, G) or components.numel() < 4 *
+            max_components or state.numel() != 7
+            or (mask is not None and tuple(mask.shape) != (G, G))):
+        raise ValueError("model and mask must be [G][G], components "
+                         "[max_components][4] int32, state [7] int32")
+    if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("mask must be uint8 or bool")
+    ptrs = (_dev_ptr(planes, "planes", torch.float32),
+            _dev_ptr(cross_psf, "cross_psf", torch.float32),
+            _dev_ptr(table, "taps", torch.float32),
+            None if mask is None else _dev_ptr(mask, "mask"),
+            _dev_ptr(model, "model", torch.float32),
+            _dev_ptr(components, "components", torch.int32),
+            _dev_ptr(state, "state", torch.int32))
+    if check_every is not None and check_every < 1:
+        raise ValueError("check_every must be at least 1")
+    chunk = nr_iterations if check_every is None else check_every
+    left = nr_iterations
+    while True:
+        n = min(chunk, left)
+        p, pp = params(n)
+        _check(lib.idg_ms_clean_launch(pp, *ptrs, _stream_handle(stream)),
+               "ms_clean")
+        left -= n
+        if left == 0:
+            break
+        with _on_stream(stream):    # the copy waits for `stream`, and only it
+            if int(state[1:2].cpu()) != 0:
+                break
+    return planes, model, components, state
+
+
+def ms_weights(cross_psf, scales, scale_bias=0.6):
+    """clean_multiscale's default (weight, inv_peak), in doubles and rounded
+    once to float32: inv_peak[s] = 1 / cross(s, s)[centre] and weight[s] =
+    (1 - scale_bias * a_s / a_max) * inv_peak[s] (the bias factor is 1 when
+    a_max = 0).  For a CUDA cross_psf the Ns centre values are copied to the
+    host, which synchronises with the current stream."""
+    Ns = len(scales)
+    Gp = cross_psf.shape[-1]
+    at = [s * Ns - s * (s - 1) // 2 for s in range(Ns)]
+    centre = cross_psf[at, Gp // 2, Gp // 2]
+    if not isinstance(centre, np.ndarray):
+        centre = centre.cpu().numpy()
+    a_max = float(max(scales))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / centre.astype(np.float64)
+        bias = np.array([1.0 if a_max == 0 else
+                         1.0 - scale_bias * float(a) / a_max for a in scales])
+        return ((bias * inv).astype(np.float32), inv.astype(np.float32))
+
+
+def clean_multiscale(residual, psf, scales=(0, 4, 8, 16), scale_bias=0.6,
+                     model=None, mask=None, gain=0.1, threshold=0.0,
+                     cycle_fraction=0.0, max_components=1000,
+                     nr_iterations=None, components=None, state=None,
+                     planes=None, cross_psf=None, check_every=None,
+                     stream=None):
+    """Multi-scale CLEAN minor cycle (Cornwell 2008): clean() with components
+    that are Gaussian blobs of the widths `scales` (pixels, ascending, the
+    first 0: the point component; a scale a has sigma = 3 a / 16).  residual,
+    psf, model, mask, gain, threshold, cycle_fraction, max_components,
+    nr_iterations, components, state, check_every: as for clean(), with
+    MS_COMPONENT_DTYPE / MS_STATE_DTYPE records (torch: int32 [., 4] and int32
+    [7]) and the threshold applying to the scale-weighted peak, which for
+    scale 0 is the residual's own value.  The model receives every
+    component's blob, so model_image() and restore() take it unchanged.
+
+    Without `planes` the scale planes and cross-PSFs are made first
+    (ms_prepare).  With `planes` and `cross_psf` from an earlier call the
+    cycle continues from them, which is how a chunked run works; `residual`
+    is then only written.  At the end `residual` receives planes[0], in
+    place.  The search weights are ms_weights(cross_psf, scales, scale_bias):
+    on the device path that is Ns floats read back once per call, after
+    prepare and before the first iteration; with check_every=None it is the
+    only read-back, and nothing is read back inside the minor cycle.
+    Returns (residual, model, components, state, planes, cross_psf)."""
+    host = isinstance(residual, np.ndarray)
+    scales = [float(a) for a in scales]
+    if (not scales or scales[0] != 0.0
+            or any(b <= a for a, b in zip(scales, scales[1:]))):
+        raise ValueError("scales must be ascending, distinct and start at 0")
+    taps = ms_scale_taps(scales)
+    if (planes is None) != (cross_psf is None):
+        raise ValueError("give planes and cross_psf together")
+    if planes is None:
+        planes, cross_psf = ms_prepare(residual, psf, taps, stream=stream)
+    if host:
+        weight, inv_peak = ms_weights(cross_psf, scales, scale_bias)
+    else:
+        with _on_stream(stream):
+            weight, inv_peak = ms_weights(cross_psf, scales, scale_bias)
+    _, model, components, state = ms_clean(
+        planes, cross_psf, taps, weight, inv_peak, model=model, mask=mask,
+        gain=gain, threshold=threshold, cycle_fraction=cycle_fraction,
+        max_components=max_components, nr_iterations=nr_iterations,
+        components=components, state=state, check_every=check_every,
+        stream=stream)
+    if host:
+        residual[...] = planes[0]
+    else:
+        with _on_stream(stream):
+            residual.copy_(planes[0])
+    return residual, model, components, state, planes, cross_psf
 
 
 # ---------------------------------------------------------------------------
