@@ -1,10 +1,12 @@
 // clean.hpp -- the arithmetic of the Hogbom minor cycle: the
 // order of peaks, the stop decision of one iteration and the subtraction of
-// one pixel.  Shared by the host twin (host::clean; host/clean.cpp) and the
-// device kernels (hip/kernels/clean_mi355x.hip.cpp), whose outputs are bit
-// for bit the same: every float operation below is one rounded float32
-// operation (the library is built -ffp-contract=off), the one fused operation
-// is an explicit fmaf, and the peak is an integer max, exact in any order.
+// one pixel.  Shared by the host twin (host::clean; host/clean.cpp over
+// host/minor_cycle.hpp) and the device kernels
+// (hip/kernels/clean_mi355x.hip.cpp over hip/kernels/minor_cycle.hpp), whose
+// outputs are bit for bit the same: every float operation below is one
+// rounded float32 operation (the library is built -ffp-contract=off), the one
+// fused operation is an explicit fmaf, and the peak is an integer max, exact
+// in any order.
 #pragma once
 
 #include <cmath>
@@ -146,6 +148,45 @@ IDG_PLAN_HD inline Patch patch_of(const Params &p, int py, int px) {
   t.x1 = t.ox + p.psf_size < p.grid_size ? t.ox + p.psf_size : p.grid_size;
   return t;
 }
+
+// The Hogbom cycle as the policy of the one minor-cycle body (host:
+// host/minor_cycle.hpp; device: hip/kernels/minor_cycle.hpp): what a cycle's
+// records are and which of the functions above it calls.  One plane and one
+// PSF patch, both known at compile time, so the body's loop over the planes
+// folds away.  ms::Cycle (common/multiscale.hpp) is the other policy.
+struct Cycle {
+  using Params = clean::Params;
+  using State = clean::State;
+  using Component = clean::Component;
+  // the clean::Params / clean::State inside the cycle's own
+  IDG_PLAN_HD static const clean::Params &base(const Params &p) { return p; }
+  IDG_PLAN_HD static const clean::State &base(const State &s) { return s; }
+  IDG_PLAN_HD static constexpr int planes(const Params &) { return 1; }
+  // the key of pixel `index` of plane q holding v; its plane and its index
+  IDG_PLAN_HD static uint64_t key_of(const Params &, int, float v,
+                                     uint32_t index, bool searchable) {
+    return clean::key_of(v, index, searchable);
+  }
+  IDG_PLAN_HD static constexpr int scale_of(uint64_t) { return 0; }
+  IDG_PLAN_HD static uint32_t index_of(uint64_t key) {
+    return clean::index_of(key);
+  }
+  IDG_PLAN_HD static bool step(State *s, const Params &p, uint64_t key,
+                               float v, float *c) {
+    return clean::step(s, p, key, v, c);
+  }
+  IDG_PLAN_HD static void set_peak(State *s, uint64_t key) {
+    clean::set_peak(s, key);
+  }
+  // where the patch that a component of scale s subtracts from plane q
+  // starts, in floats from the PSF buffer's first
+  IDG_PLAN_HD static constexpr size_t psf_at(const Params &, int, int) {
+    return 0;
+  }
+  IDG_PLAN_HD static Component record(int y, int x, int, float c) {
+    return {y, x, c};
+  }
+};
 
 }  // namespace clean
 }  // namespace idg_mi355x

@@ -4,7 +4,8 @@
 // cross-PSF of two scales is stored.  Shared by the host twin
 // (host/multiscale.cpp) and the device kernels
 // (hip/kernels/multiscale_mi355x.hip.cpp), whose outputs are bit for bit the
-// same.  The key's magnitude bits, the stop decision, the patch and the
+// same; the minor cycle's loop is the one both CLEANs share
+// (host/minor_cycle.hpp, hip/kernels/minor_cycle.hpp).  The key's magnitude bits, the stop decision, the patch and the
 // subtraction of one pixel are those of common/clean.hpp, used from there:
 // with one scale of weight 1 an iteration is a Hogbom iteration.
 #pragma once
@@ -113,6 +114,42 @@ IDG_PLAN_HD inline float model_add(float c, float hy, float hx, float model) {
   const float b = a * hx;
   return model + b;
 }
+
+// Multi-scale CLEAN as the policy of the one minor-cycle body (clean::Cycle,
+// common/clean.hpp, names the members): nr_scales planes, the key carries the
+// scale, and a component of scale s subtracts cross(s, q) from plane q.
+struct Cycle {
+  using Params = ms::Params;
+  using State = ms::State;
+  using Component = ms::Component;
+  IDG_PLAN_HD static const clean::Params &base(const Params &p) {
+    return p.base;
+  }
+  IDG_PLAN_HD static const clean::State &base(const State &st) { return st.s; }
+  IDG_PLAN_HD static int planes(const Params &p) { return p.nr_scales; }
+  IDG_PLAN_HD static uint64_t key_of(const Params &p, int q, float v,
+                                     uint32_t index, bool searchable) {
+    return ms::key_of(weighted(p, q, v), q, index, searchable);
+  }
+  IDG_PLAN_HD static int scale_of(uint64_t key) { return ms::scale_of(key); }
+  IDG_PLAN_HD static uint32_t index_of(uint64_t key) {
+    return ms::index_of(key);
+  }
+  IDG_PLAN_HD static bool step(State *st, const Params &p, uint64_t key,
+                               float v, float *c) {
+    return ms::step(st, p, key, v, c);
+  }
+  IDG_PLAN_HD static void set_peak(State *st, uint64_t key) {
+    ms::set_peak(st, key);
+  }
+  IDG_PLAN_HD static size_t psf_at(const Params &p, int s, int q) {
+    const size_t Gp = static_cast<size_t>(p.base.psf_size);
+    return cross_at(p.nr_scales, s, q) * (Gp * Gp);
+  }
+  IDG_PLAN_HD static Component record(int y, int x, int s, float c) {
+    return {y, x, s, c};
+  }
+};
 
 }  // namespace ms
 }  // namespace idg_mi355x

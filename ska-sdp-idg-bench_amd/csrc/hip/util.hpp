@@ -355,8 +355,9 @@ hipError_t launch_weight_apply(const weight::Geometry &geometry,
                                float *d_imaging_weights, void *d_out,
                                double *d_sum_weights, hipStream_t stream);
 
-// The Hogbom minor cycle on the device (kernels/clean_mi355x.hip.cpp; DESIGN.md
-// §15), bit for bit the host entry of common/clean.hpp's arithmetic: one
+// The Hogbom minor cycle on the device (kernels/clean_mi355x.hip.cpp over the
+// shared body of kernels/minor_cycle.hpp), bit for bit the
+// host entry of common/clean.hpp's arithmetic: one
 // search launch, params.nr_iterations iteration launches (each subtracts one
 // component and searches for the next in the same pass) and one finish launch,
 // continuing from *d_state (clean::State) and leaving it there.  The tiles'
@@ -376,7 +377,8 @@ hipError_t launch_clean(const clean::Params &params, float *d_residual,
 // launch_convolve_separable: the row pass into d_tmp and the column pass into
 // d_out (which may be d_in), two launches, no workspace.  launch_ms_prepare:
 // the scale planes and the cross-PSFs, launches of those two passes and one
-// device-to-device copy.  launch_ms_clean: one search launch,
+// device-to-device copy.  launch_ms_clean (the shared body of
+// kernels/minor_cycle.hpp under ms::Cycle): one search launch,
 // params.base.nr_iterations iteration launches and one finish launch,
 // continuing from *d_state (ms::State) and leaving it there; the tiles'
 // partials and the double-buffered state live on a kWorkspaceMultiscale

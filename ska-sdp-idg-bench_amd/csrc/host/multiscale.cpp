@@ -1,36 +1,18 @@
 // multiscale.cpp -- the host twins of multi-scale CLEAN (host.hpp): the scale
-// taps, the dense separable convolution, the prepare step and the minor cycle.
+// taps, the dense separable convolution, the prepare step and the minor cycle
+// (the one of host/minor_cycle.hpp under ms::Cycle).
 #include <algorithm>
 #include <vector>
 
 #include "host/host.hpp"
+#include "host/minor_cycle.hpp"
 
 namespace idg_mi355x {
 namespace host {
 
 namespace {
 
-namespace cl = idg_mi355x::clean;
-
 double scale_sigma(double scale) { return scale * 3.0 / 16.0; }
-
-// The key of the planes' peak (ms::key_of; 0: none).
-uint64_t ms_peak(const ms::Params &p, const float *planes,
-                 const uint8_t *mask) {
-  const size_t cells =
-      static_cast<size_t>(p.base.grid_size) * p.base.grid_size;
-  uint64_t best = 0;
-  for (int s = 0; s < p.nr_scales; ++s) {
-    const float *plane = planes + s * cells;
-    for (size_t i = 0; i < cells; ++i) {
-      const uint64_t key =
-          ms::key_of(ms::weighted(p, s, plane[i]), s, static_cast<uint32_t>(i),
-                     mask == nullptr || mask[i] != 0);
-      if (key > best) best = key;
-    }
-  }
-  return best;
-}
 
 }  // namespace
 
@@ -108,48 +90,19 @@ std::string ms_clean(const ms::Params &p, float *planes,
                      const float *cross_psf, const float *taps,
                      const uint8_t *mask, float *model,
                      ms::Component *components, ms::State *state) {
-  ms::State st = *state;
-  if (!cl::state_ok(st.s, p.base))
-    return "idg_ms_clean: state.n_components " +
-           std::to_string(st.s.n_components) + " outside [0, " +
-           std::to_string(p.base.max_components) + "]";
-  const int Gi = p.base.grid_size;
-  const size_t G = static_cast<size_t>(Gi);
-  const size_t Gp = static_cast<size_t>(p.base.psf_size);
-  const size_t cells = G * G, pcells = Gp * Gp;
-  uint64_t key = 0;
-  for (int k = 0;; ++k) {
-    key = ms_peak(p, planes, mask);
-    if (k == p.base.nr_iterations) break;
-    float c = 0.0f;
-    const uint32_t index = key != 0 ? ms::index_of(key) : 0;
-    const int s = key != 0 ? ms::scale_of(key) : 0;
-    if (!ms::step(&st, p, key, key != 0 ? planes[s * cells + index] : 0.0f, &c))
-      break;
-    const int py = static_cast<int>(index / G), px = static_cast<int>(index % G);
-    components[st.s.n_components - 1] = {py, px, s, c};
-    const int r = p.radius[s];
-    const float *h = taps + ms::taps_at(p, s);
-    for (int y = std::max(py - r, 0); y <= std::min(py + r, Gi - 1); ++y)
-      for (int x = std::max(px - r, 0); x <= std::min(px + r, Gi - 1); ++x) {
-        float *m = model + y * G + x;
-        *m = ms::model_add(c, h[y - py + r], h[x - px + r], *m);
-      }
-    const cl::Patch pt = cl::patch_of(p.base, py, px);
-    for (int q = 0; q < p.nr_scales; ++q) {
-      float *plane = planes + q * cells;
-      const float *cross = cross_psf + ms::cross_at(p.nr_scales, s, q) * pcells;
-      for (int y = pt.y0; y < pt.y1; ++y) {
-        float *row = plane + static_cast<size_t>(y) * G;
-        const float *prow = cross + static_cast<size_t>(y - pt.oy) * Gp;
-        for (int x = pt.x0; x < pt.x1; ++x)
-          row[x] = cl::subtract(c, prow[x - pt.ox], row[x]);
-      }
-    }
-  }
-  ms::set_peak(&st, key);
-  *state = st;
-  return {};
+  const int G = p.base.grid_size;
+  // step 7: the component's footprint, clipped at the image's edge
+  return minor_cycle<ms::Cycle>(
+      "idg_ms_clean", p, planes, cross_psf, mask, components, state,
+      [&](float c, int s, uint32_t, int py, int px) {
+        const int r = p.radius[s];
+        const float *h = taps + ms::taps_at(p, s);
+        for (int y = std::max(py - r, 0); y <= std::min(py + r, G - 1); ++y)
+          for (int x = std::max(px - r, 0); x <= std::min(px + r, G - 1); ++x) {
+            float *m = model + static_cast<size_t>(y) * G + x;
+            *m = ms::model_add(c, h[y - py + r], h[x - px + r], *m);
+          }
+      });
 }
 
 }  // namespace host

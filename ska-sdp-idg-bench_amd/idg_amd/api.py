@@ -1136,7 +1136,85 @@ def _square(a, name):
     return a.shape[0]
 
 
-def clean(residual, psf, model=None, mask=None, gain=0.1, threshold=0.0,
+def _minor_cycle(what, entries, params, lead, G, dtypes, model, mask,
+                 max_components, nr_iterations, components, state,
+                 check_every, stream):
+    """What clean() and ms_clean() share.  entries: the (host, _launch) pair
+    of the C ABI, called as entry(params(n)[1], *lead, mask, model,
+    components, state[, stream]) for n iterations; lead: the (buffer, name,
+    written) triples the entry takes first, all float32, numpy for the host
+    entry; dtypes: the numpy (component, state) records.  Makes the model,
+    components and state that are None, refuses wrong shapes and dtypes,
+    passes a bool mask as uint8 and, on the device, enqueues check_every
+    iterations at a time.  Returns (model, components, state)."""
+    host = isinstance(lead[0][0], np.ndarray)
+    records = max(max_components, 1)     # (never a null pointer)
+    if host:
+        if model is None:
+            model = np.zeros((G, G), np.float32)
+        if components is None:
+            components = np.zeros(records, dtypes[0])
+        if state is None:
+            state = np.zeros(1, dtypes[1])
+        if (model.shape != (G, G) or components.size < max_components
+                or state.size != 1
+                or (mask is not None and mask.shape != (G, G))):
+            raise ValueError("model and mask must be [G][G], components "
+                             "[max_components], state [1]")
+        if mask is not None and mask.dtype == np.bool_:
+            mask = mask.view(np.uint8)
+        p, pp = params(nr_iterations)
+        _check(entries[0](
+            pp, *(_np_ptr(a, np.float32, name, written)
+                  for a, name, written in lead),
+            None if mask is None else _np_ptr(mask, np.uint8, "mask"),
+            _np_ptr(model, np.float32, "model", True),
+            _np_ptr(components, dtypes[0], "components", True),
+            _np_ptr(state, dtypes[1], "state", True)), what)
+        return model, components, state
+    import torch
+    dev = lead[0][0].device
+    # a record as int32s
+    width, fields = dtypes[0].itemsize // 4, dtypes[1].itemsize // 4
+    with _on_stream(stream):
+        if model is None:
+            model = torch.zeros((G, G), dtype=torch.float32, device=dev)
+        if components is None:
+            components = torch.zeros((records, width), dtype=torch.int32,
+                                     device=dev)
+        if state is None:
+            state = torch.zeros(fields, dtype=torch.int32, device=dev)
+    if (tuple(model.shape) != (G, G) or components.numel() < width *
+            max_components or state.numel() != fields
+            or (mask is not None and tuple(mask.shape) != (G, G))):
+        raise ValueError("model and mask must be [G][G], components "
+                         f"[max_components][{width}] int32, state [{fields}] "
+                         "int32")
+    if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("mask must be uint8 or bool")
+    ptrs = [_dev_ptr(a, name, torch.float32) for a, name, _ in lead] + [
+        None if mask is None else _dev_ptr(mask, "mask"),
+        _dev_ptr(model, "model", torch.float32),
+        _dev_ptr(components, "components", torch.int32),
+        _dev_ptr(state, "state", torch.int32)]
+    if check_every is not None and check_every < 1:
+        raise ValueError("check_every must be at least 1")
+    chunk = nr_iterations if check_every is None else check_every
+    left = nr_iterations
+    while True:
+        n = min(chunk, left)
+        p, pp = params(n)
+        _check(entries[1](pp, *ptrs, _stream_handle(stream)), what)
+        left -= n
+        if left == 0:
+            break
+        with _on_stream(stream):    # the copy waits for `stream`, and only it
+            if int(state[1:2].cpu()) != 0:
+                break
+    return model, components, state
+
+
+def clean(residual, psf,model=None, mask=None, gain=0.1, threshold=0.0,
           cycle_fraction=0.0, max_components=1000, nr_iterations=None,
           components=None, state=None, check_every=None, stream=None):
     """Hogbom minor cycle (idg_clean / idg_clean_launch): up to nr_iterations
@@ -1157,74 +1235,18 @@ def clean(residual, psf, model=None, mask=None, gain=0.1, threshold=0.0,
     state.reason read back between the chunks, to stop enqueueing once it is
     set; None reads nothing back.  Returns (residual, model, components,
     state)."""
-    host = isinstance(residual, np.ndarray)
     G, Gp = _square(residual, "residual"), _square(psf, "psf")
     if nr_iterations is None:
         nr_iterations = max_components
-    records = max(max_components, 1)     # (never a null pointer)
-    if host:
-        if model is None:
-            model = np.zeros((G, G), np.float32)
-        if components is None:
-            components = np.zeros(records, COMPONENT_DTYPE)
-        if state is None:
-            state = np.zeros(1, STATE_DTYPE)
-        if (model.shape != residual.shape or components.size < max_components
-                or state.size != 1
-                or (mask is not None and mask.shape != residual.shape)):
-            raise ValueError("model and mask must be [G][G], components "
-                             "[max_components], state [1]")
-        if mask is not None and mask.dtype == np.bool_:
-            mask = mask.view(np.uint8)
-        p, pp = _clean_params(G, Gp, max_components, nr_iterations, gain,
-                              threshold, cycle_fraction)
-        _check(lib.idg_clean(
-            pp, _np_ptr(residual, np.float32, "residual", True),
-            _np_ptr(psf, np.float32, "psf"),
-            None if mask is None else _np_ptr(mask, np.uint8, "mask"),
-            _np_ptr(model, np.float32, "model", True),
-            _np_ptr(components, COMPONENT_DTYPE, "components", True),
-            _np_ptr(state, STATE_DTYPE, "state", True)), "clean")
-        return residual, model, components, state
-    import torch
-    dev = residual.device
-    with _on_stream(stream):
-        if model is None:
-            model = torch.zeros((G, G), dtype=torch.float32, device=dev)
-        if components is None:
-            components = torch.zeros((records, 3), dtype=torch.int32,
-                                     device=dev)
-        if state is None:
-            state = torch.zeros(6, dtype=torch.int32, device=dev)
-    if (model.shape != residual.shape or components.numel() < 3 *
-            max_components or state.numel() != 6
-            or (mask is not None and mask.shape != residual.shape)):
-        raise ValueError("model and mask must be [G][G], components "
-                         "[max_components][3] int32, state [6] int32")
-    if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
-        raise TypeError("mask must be uint8 or bool")
-    ptrs = (_dev_ptr(residual, "residual", torch.float32),
-            _dev_ptr(psf, "psf", torch.float32),
-            None if mask is None else _dev_ptr(mask, "mask"),
-            _dev_ptr(model, "model", torch.float32),
-            _dev_ptr(components, "components", torch.int32),
-            _dev_ptr(state, "state", torch.int32))
-    if check_every is not None and check_every < 1:
-        raise ValueError("check_every must be at least 1")
-    chunk = nr_iterations if check_every is None else check_every
-    left = nr_iterations
-    while True:
-        n = min(chunk, left)
-        p, pp = _clean_params(G, Gp, max_components, n, gain, threshold,
-                              cycle_fraction)
-        _check(lib.idg_clean_launch(pp, *ptrs, _stream_handle(stream)),
-               "clean")
-        left -= n
-        if left == 0:
-            break
-        with _on_stream(stream):    # the copy waits for `stream`, and only it
-            if int(state[1:2].cpu()) != 0:
-                break
+
+    def params(n):
+        return _clean_params(G, Gp, max_components, n, gain, threshold,
+                             cycle_fraction)
+    model, components, state = _minor_cycle(
+        "clean", (lib.idg_clean, lib.idg_clean_launch), params,
+        [(residual, "residual", True), (psf, "psf", False)], G,
+        (COMPONENT_DTYPE, STATE_DTYPE), model, mask, max_components,
+        nr_iterations, components, state, check_every, stream)
     return residual, model, components, state
 
 
@@ -1418,75 +1440,18 @@ def ms_clean(planes, cross_psf, taps, weight, inv_peak, model=None, mask=None,
                          "the number of scales")
     if nr_iterations is None:
         nr_iterations = max_components
-    records = max(max_components, 1)     # (never a null pointer)
 
     def params(n):
         return _ms_params(G, Gp, radii, max_components, n, gain, threshold,
                           cycle_fraction, weight, inv_peak)
-    if host:
-        if model is None:
-            model = np.zeros((G, G), np.float32)
-        if components is None:
-            components = np.zeros(records, MS_COMPONENT_DTYPE)
-        if state is None:
-            state = np.zeros(1, MS_STATE_DTYPE)
-        if (model.shape != (G, G) or components.size < max_components
-                or state.size != 1
-                or (mask is not None and mask.shape != (G, G))):
-            raise ValueError("model and mask must be [G][G], components "
-                             "[max_components], state [1]")
-        if mask is not None and mask.dtype == np.bool_:
-            mask = mask.view(np.uint8)
-        p, pp = params(nr_iterations)
-        _check(lib.idg_ms_clean(
-            pp, _np_ptr(planes, np.float32, "planes", True),
-            _np_ptr(cross_psf, np.float32, "cross_psf"),
-            _np_ptr(table, np.float32, "taps"),
-            None if mask is None else _np_ptr(mask, np.uint8, "mask"),
-            _np_ptr(model, np.float32, "model", True),
-            _np_ptr(components, MS_COMPONENT_DTYPE, "components", True),
-            _np_ptr(state, MS_STATE_DTYPE, "state", True)), "ms_clean")
-        return planes, model, components, state
-    import torch
-    dev = planes.device
-    table = _to_device(table, planes, stream)
-    with _on_stream(stream):
-        if model is None:
-            model = torch.zeros((G, G), dtype=torch.float32, device=dev)
-        if components is None:
-            components = torch.zeros((records, 4), dtype=torch.int32,
-                                     device=dev)
-        if state is None:
-            state = torch.zeros(7, dtype=torch.int32, device=dev)
-    if (tuple(model.shape) != (G, G) or components.numel() < 4 *
-            max_components or state.numel() != 7
-            or (mask is not None and tuple(mask.shape) != (G, G))):
-        raise ValueError("model and mask must be [G][G], components "
-                         "[max_components][4] int32, state [7] int32")
-    if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
-        raise TypeError("mask must be uint8 or bool")
-    ptrs = (_dev_ptr(planes, "planes", torch.float32),
-            _dev_ptr(cross_psf, "cross_psf", torch.float32),
-            _dev_ptr(table, "taps", torch.float32),
-            None if mask is None else _dev_ptr(mask, "mask"),
-            _dev_ptr(model, "model", torch.float32),
-            _dev_ptr(components, "components", torch.int32),
-            _dev_ptr(state, "state", torch.int32))
-    if check_every is not None and check_every < 1:
-        raise ValueError("check_every must be at least 1")
-    chunk = nr_iterations if check_every is None else check_every
-    left = nr_iterations
-    while True:
-        n = min(chunk, left)
-        p, pp = params(n)
-        _check(lib.idg_ms_clean_launch(pp, *ptrs, _stream_handle(stream)),
-               "ms_clean")
-        left -= n
-        if left == 0:
-            break
-        with _on_stream(stream):    # the copy waits for `stream`, and only it
-            if int(state[1:2].cpu()) != 0:
-                break
+    if not host:
+        table = _to_device(table, planes, stream)
+    model, components, state = _minor_cycle(
+        "ms_clean", (lib.idg_ms_clean, lib.idg_ms_clean_launch), params,
+        [(planes, "planes", True), (cross_psf, "cross_psf", False),
+         (table, "taps", False)], G, (MS_COMPONENT_DTYPE, MS_STATE_DTYPE),
+        model, mask, max_components, nr_iterations, components, state,
+        check_every, stream)
     return planes, model, components, state
 
 

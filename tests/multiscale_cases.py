@@ -307,6 +307,12 @@ MS = {
     "G260_Gp65_footprint_across_tiles": lambda: ms_case(
         260, 65, (0, 4, 8), [(8, 256, 3.0, 1.5), (135, 255, -4.0, 0.75)],
         chunks=(6,), gain=0.5),
+    # G % 4 == 2: the device's one-pixel-per-lane form on planes of its own
+    # (every other case has G % 4 == 0).  The host entry takes components of
+    # scale 2 at the blob and of scale 0 at the point, in turns.
+    "G66_Gp33_scalar_form": lambda: ms_case(
+        66, 33, (0, 4, 8), [(20, 41, 0.3, 3.0), (50, 11, 3.0, 0)],
+        chunks=(3, 4)),
     "tie_between_scales_lower_scale_wins": lambda: ms_case(
         64, 9, (0, 4), [], chunks=(3,), unit_weight=True,
         edit=_set((1, 10, 30, 7.0), (0, 25, 5, 7.0))),

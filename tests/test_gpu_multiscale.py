@@ -210,6 +210,14 @@ def test_same_bytes_on_a_stream(idg, name):
 
 
 @pytest.mark.parametrize("name", ["G260_Gp65_footprint_across_tiles",
+                                  "G66_Gp33_scalar_form"])
+def test_same_bytes_with_every_tile_rescanning(idg, name, monkeypatch):
+    c, i, host = _case(idg, name)
+    monkeypatch.setenv("IDG_CLEAN_RESCAN", "1")
+    assert mc.same_bytes(_run_device(idg, c, i), host) == []
+
+
+@pytest.mark.parametrize("name", ["G260_Gp65_footprint_across_tiles",
                                   "stop_below_level", "stop_components_full",
                                   "chunks_3_4_5"])
 def test_check_every_4_is_check_every_none(idg, name):

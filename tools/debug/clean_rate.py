@@ -67,7 +67,7 @@ def inputs(G, Gp, seed=1):
 
 
 def tile_rows(G):
-    """Rows of a tile (clean_mi355x.hip.cpp tiling_of): 256 columns wide, at
+    """Rows of a tile (kernels/minor_cycle.hpp tiling_of): 256 columns wide, at
     least 8 rows, at most 2048 tiles."""
     tiles_x = -(-G // 256)
     return max(8, -(-G // (2048 // tiles_x)))
