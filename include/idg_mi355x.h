@@ -715,6 +715,103 @@ int idg_clean_launch(const idg_clean_params_t *params, float *residual,
                      idg_clean_component_t *components,
                      idg_clean_state_t *state, void *stream);
 
+/* ---- Clark CLEAN: many components per launch on a candidate list
+ * The minor cycle of idg_clean on the few thousand brightest pixels alone
+ * (Clark 1980): a round selects them, runs the cycle on that list, and then
+ * subtracts the components it found from the whole residual.  On the device
+ * the list lives in the registers of one workgroup, so a round of thousands
+ * of components is a fixed handful of launches.  No reference counterpart;
+ * idg_clark (host pointers, no device needed) and idg_clark_launch (device
+ * pointers, asynchronous on `stream`, nothing read back, scratch from the
+ * workspace cache) produce the same bytes in every output.
+ *
+ * residual, psf, mask, model and components are idg_clean's, with the same
+ * meaning: the mask limits which pixels may become candidates, never what is
+ * subtracted.  state: idg_clark_state_t, zeroed by the caller before the first
+ * call; every later call continues from it: k calls of n rounds give exactly
+ * the bytes of one call of k * n.  All arithmetic is float32, every operation
+ * rounded once, the one fused operation idg_clean's step 7.
+ *
+ * One round, run while reason == 0 (rounds counts the rounds begun):
+ *   1. Peak.  P: the signed value at the residual's peak, as idg_clean defines
+ *      it.  No peak: reason = IDG_CLEAN_NO_PEAK, the round ends.  started ==
+ *      0: level = fmaxf(threshold, cycle_fraction * |P|), started = 1.
+ *      !(|P| > level): reason = IDG_CLEAN_BELOW_LEVEL, the round ends.
+ *   2. Limit.  f = fmaxf(level, select_fraction * |P|) (one rounded multiply).
+ *      A pixel's bin is (bits(|s|) >> 19), 4096 bins: the exponent and four
+ *      mantissa bits.  hist[b]: the searchable, non-NaN pixels of bin b.  b*:
+ *      the least bin with sum_{b >= b*} hist[b] <= max_candidates (4096 when
+ *      even the top occupied bin overflows).  tbits = max(bits(f) + 1,
+ *      b* << 19) as unsigned 32-bit integers; round_limit = the float with
+ *      those bits.
+ *   3. Candidates: the searchable, non-NaN pixels with bits(|s|) >= tbits, at
+ *      most max_candidates by construction; n_candidates = their number.
+ *      None: reason = IDG_CLARK_NO_CANDIDATE, the round ends.  The list is a
+ *      set: no output depends on its order.
+ *   4. Cycle, at most iterations_per_round times: the list's peak (largest
+ *      |value|, ties to the lowest linear index).  None, or its bits(|value|)
+ *      < tbits: the round goes to step 5 with reason still 0.  Otherwise
+ *      steps 3 to 6 of idg_clean's iteration on it (a stop there -- only
+ *      IDG_CLEAN_COMPONENTS_FULL can occur -- sends the round to step 5 with
+ *      that reason), and for every list entry (y, x) inside the component's
+ *      patch: value = fmaf(-c, psf[dy][dx], value).
+ *   5. Apply: the components this round recorded are subtracted from the
+ *      whole residual, each over its patch as idg_clean's step 7, at every
+ *      pixel in record order.  A round that took no component leaves the
+ *      residual untouched.
+ * After the call state.peak and state.peak_index describe the residual as it
+ * stands, as for idg_clean; nr_rounds = 0 refreshes those two and nothing
+ * else.
+ *
+ * What follows: (A) the residual is, bit for bit, the one from which the same
+ * components were subtracted one at a time by idg_clean's step 7; (B) after a
+ * round's apply the residual at every candidate equals that candidate's final
+ * list value; (C) whenever the whole residual's peak is a list member at every
+ * iteration, components, model, residual and n_components are idg_clean's.
+ *
+ * IDG_E_INVALID_ARGUMENT (every buffer left as it was): idg_clean's list with
+ * nr_rounds and iterations_per_round in place of nr_iterations (both >= 0),
+ * select_fraction not finite or outside [0, 1], max_candidates outside
+ * [1, 16384]; on a state with n_components outside [0, max_components] the
+ * _launch form, which reads nothing back, runs no round. */
+#define IDG_CLARK_NO_CANDIDATE 4 /* state.reason, beside IDG_CLEAN_*          */
+
+typedef struct idg_clark_params_t {
+  uint32_t struct_size; /* sizeof(idg_clark_params_t)                        */
+  int32_t grid_size;    /* G                                                 */
+  int32_t psf_size;     /* Gp                                                */
+  int32_t max_components;
+  int32_t nr_rounds;    /* rounds of this call                               */
+  int32_t iterations_per_round;
+  int32_t max_candidates; /* 1 .. 16384                                      */
+  float gain;
+  float threshold;
+  float cycle_fraction;
+  float select_fraction; /* in [0, 1]                                        */
+} idg_clark_params_t;
+
+typedef struct idg_clark_state_t {
+  int32_t n_components; /* the six fields of idg_clean_state_t               */
+  int32_t reason;       /* IDG_CLEAN_* or IDG_CLARK_NO_CANDIDATE             */
+  int32_t started;
+  int32_t peak_index;
+  float level;
+  float peak;
+  int32_t n_candidates; /* of the last round that reached step 3             */
+  float round_limit;    /* of the last round that reached step 2             */
+  int32_t rounds;       /* rounds begun so far                               */
+} idg_clark_state_t;
+
+int idg_clark(const idg_clark_params_t *params, float *residual,
+              const float *psf, const uint8_t *mask, float *model,
+              idg_clean_component_t *components, idg_clark_state_t *state);
+/* Five launches per round plus three: a caller who wants to stop early reads
+ * state->reason between calls of a few rounds each. */
+int idg_clark_launch(const idg_clark_params_t *params, float *residual,
+                     const float *psf, const uint8_t *mask, float *model,
+                     idg_clean_component_t *components,
+                     idg_clark_state_t *state, void *stream);
+
 /* ---- restore: clean beam and restored image --------------------
  * model and residual -> the image an imager hands over: the model convolved
  * with a Gaussian clean beam fitted to the PSF's main lobe, plus the residual.

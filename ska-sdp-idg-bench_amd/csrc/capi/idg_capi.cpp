@@ -261,6 +261,52 @@ static_assert(IDG_CLEAN_RUNNING == idg_mi355x::clean::kRunning &&
                   sizeof(idg_clean_state_t) == 24,
               "idg_clean_* records are clean:: records");
 
+// idg_clark_params_t (read_struct) -> clark::Params.
+int parse_clark(const idg_clark_params_t *params,
+                idg_mi355x::clark::Params *out) {
+  idg_clark_params_t v;
+  if (int rc = read_struct(params, "idg_clark_params_t", &v)) return rc;
+  if (v.psf_size < 1 || v.grid_size < v.psf_size ||
+      v.grid_size > idg_mi355x::clean::kMaxGridSize)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clark: 1 <= psf_size <= grid_size <= 16384 required");
+  if (!std::isfinite(v.gain) || !std::isfinite(v.threshold) ||
+      !std::isfinite(v.cycle_fraction) || v.threshold < 0.0f ||
+      v.cycle_fraction < 0.0f)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clark: gain, threshold and cycle_fraction must be finite, "
+                "threshold and cycle_fraction not negative");
+  if (!std::isfinite(v.select_fraction) || v.select_fraction < 0.0f ||
+      v.select_fraction > 1.0f)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clark: select_fraction must be in [0, 1]");
+  if (v.nr_rounds < 0 || v.iterations_per_round < 0 || v.max_components < 0)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clark: nr_rounds >= 0, iterations_per_round >= 0 and "
+                "max_components >= 0 required");
+  if (v.max_candidates < 1 ||
+      v.max_candidates > idg_mi355x::clark::kMaxCandidates)
+    return fail(IDG_E_INVALID_ARGUMENT,
+                "clark: 1 <= max_candidates <= 16384 required");
+  out->base.grid_size = v.grid_size;
+  out->base.psf_size = v.psf_size;
+  out->base.max_components = v.max_components;
+  out->base.nr_iterations = 0;
+  out->base.gain = v.gain;
+  out->base.threshold = v.threshold;
+  out->base.cycle_fraction = v.cycle_fraction;
+  out->nr_rounds = v.nr_rounds;
+  out->iterations_per_round = v.iterations_per_round;
+  out->max_candidates = v.max_candidates;
+  out->select_fraction = v.select_fraction;
+  return IDG_OK;
+}
+static_assert(IDG_CLARK_NO_CANDIDATE == idg_mi355x::clark::kNoCandidate &&
+                  sizeof(idg_clark_state_t) ==
+                      sizeof(idg_mi355x::clark::State) &&
+                  sizeof(idg_clark_state_t) == 36,
+              "idg_clark_state_t is clark::State");
+
 // Half-open byte ranges of a call's buffers: `who`: "a and b overlap" for the
 // first pair that does and is not listed in `may` (pairs of indices that may
 // be the same pointer).  Null buffers are skipped.
@@ -1159,6 +1205,37 @@ int idg_clean_launch(const idg_clean_params_t *params, float *residual,
                                            components, state,
                                            static_cast<hipStream_t>(stream)),
                   "idg_clean_launch");
+}
+
+int idg_clark(const idg_clark_params_t *params, float *residual,
+              const float *psf, const uint8_t *mask, float *model,
+              idg_clean_component_t *components, idg_clark_state_t *state) {
+  idg_mi355x::clark::Params p;
+  if (int rc = parse_clark(params, &p)) return rc;
+  if (int rc = clean_buffers("idg_clark", residual, psf, model, components,
+                             state))
+    return rc;
+  const std::string msg = idg_mi355x::host::clark(
+      p, residual, psf, mask, model,
+      reinterpret_cast<idg_mi355x::clean::Component *>(components),
+      reinterpret_cast<idg_mi355x::clark::State *>(state));
+  if (!msg.empty()) return fail(IDG_E_INVALID_ARGUMENT, msg);
+  return IDG_OK;
+}
+
+int idg_clark_launch(const idg_clark_params_t *params, float *residual,
+                     const float *psf, const uint8_t *mask, float *model,
+                     idg_clean_component_t *components,
+                     idg_clark_state_t *state, void *stream) {
+  idg_mi355x::clark::Params p;
+  if (int rc = parse_clark(params, &p)) return rc;
+  if (int rc = clean_buffers("idg_clark_launch", residual, psf, model,
+                             components, state))
+    return rc;
+  return from_hip(idg_mi355x::launch_clark(p, residual, psf, mask, model,
+                                           components, state,
+                                           static_cast<hipStream_t>(stream)),
+                  "idg_clark_launch");
 }
 
 int idg_beam_from_axes(double major, double minor, double pa,

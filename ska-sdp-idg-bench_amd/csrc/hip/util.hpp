@@ -83,7 +83,7 @@ void print_benchmark();
 // ---------------------------------------------------------------------------
 // MI355X runtime: kernel selection, validation and raw-pointer pipelines.
 // Used by the kernel TUs, by util.cpp and by the C ABI (capi/idg_capi.cpp);
-// the host twins of launch_plan, _weight_*, _clean and _restore are in
+// the host twins of launch_plan, _weight_*, _clean, _clark and _restore are in
 // host/host.hpp.
 // ---------------------------------------------------------------------------
 namespace idg_mi355x {
@@ -190,7 +190,7 @@ hipError_t launch_parts(const KernelChoice &k, int nr_subgrids, void **args13,
 constexpr int kWorkspaceQueue = 0, kWorkspaceHomeSort = 1,
               kWorkspaceAdderSeg = 2, kWorkspaceAuto = 3, kWorkspacePlan = 4,
               kWorkspaceWeight = 5, kWorkspaceClean = 6,
-              kWorkspaceMultiscale = 7;
+              kWorkspaceMultiscale = 7, kWorkspaceClark = 8;
 // Not copyable: a copy would release the slot twice.
 struct WorkspaceLease {
   void *ptr = nullptr;
@@ -401,6 +401,23 @@ hipError_t launch_ms_clean(const ms::Params &params, float *d_planes,
                            const uint8_t *d_mask, float *d_model,
                            void *d_components, void *d_state,
                            hipStream_t stream);
+
+// Clark CLEAN on the device (kernels/clark_mi355x.hip.cpp), bit
+// for bit the host entry of common/clark.hpp's arithmetic: params.nr_rounds
+// rounds of five launches each (histogram and peak, limit, compaction, the
+// one-workgroup minor cycle on the candidate list, apply) between a begin
+// launch and a search and a finish launch, continuing from *d_state
+// (clark::State) and leaving it there.  The partials, the histogram, the
+// candidate list and the state live on a kWorkspaceClark lease; nothing is
+// read back.  d_mask may be null; d_components: clean::Component
+// [params.base.max_components].
+namespace clark {
+struct Params;
+}
+hipError_t launch_clark(const clark::Params &params, float *d_residual,
+                        const float *d_psf, const uint8_t *d_mask,
+                        float *d_model, void *d_components, void *d_state,
+                        hipStream_t stream);
 
 // The restore step on the device (kernels/restore_mi355x.hip.cpp; DESIGN.md
 // §16), bit for bit the host entry of common/restore.hpp's arithmetic: one

@@ -1,7 +1,7 @@
 // host.hpp -- the host twins of the device steps: the plan walk, the imaging
-// weights, the Hogbom minor cycle, multi-scale CLEAN, the restore step and the
-// taper's image.  Plain C++ over the per-element rules of
-// common/{plan,weight,clean,multiscale,restore}.hpp, no HIP call, so they
+// weights, the Hogbom minor cycle, multi-scale CLEAN, Clark CLEAN, the restore
+// step and the taper's image.  Plain C++ over the per-element rules of
+// common/{plan,weight,clean,multiscale,clark,restore}.hpp, no HIP call, so they
 // run (and compile) without a GPU; the GPU suites compare the device kernels
 // against them bit for bit.  Each takes the parsed values its launch_*
 // counterpart (hip/util.hpp) takes; the C ABI (capi/idg_capi.cpp) validates
@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <string>
 
+#include "common/clark.hpp"
 #include "common/clean.hpp"
 #include "common/multiscale.hpp"
 #include "common/plan.hpp"
@@ -114,6 +115,14 @@ std::string ms_clean(const ms::Params &params, float *planes,
                      const float *cross_psf, const float *taps,
                      const uint8_t *mask, float *model,
                      ms::Component *components, ms::State *state);
+
+// host/clark.cpp.  params.nr_rounds rounds from *state, each
+// at most params.iterations_per_round components on a candidate list, then
+// subtracted from the whole residual; mask may be null.  Not empty: the state
+// no round may run from (clean::state_ok), every buffer left as it was.
+std::string clark(const clark::Params &params, float *residual,
+                  const float *psf, const uint8_t *mask, float *model,
+                  clean::Component *components, clark::State *state);
 
 // host/image.cpp.  out[G][G]: the [S][S] taper interpolated
 // to the image's pixels, in doubles.

@@ -21,12 +21,14 @@ from .api import (IMAGE_SIZE, METADATA_DTYPE, NR_CORRELATIONS, W_STEP,
                   psf, weigh, weight_apply, weight_density, weight_scheme,
                   CLEAN_REASONS, COMPONENT_DTYPE, STATE_DTYPE, clean,
                   model_image, stokes_i,
+                  CLARK_REASONS, CLARK_STATE_DTYPE, clark,
                   Beam, beam_fit, beam_from_axes, beam_radius, beam_taps,
                   restore,
                   MS_COMPONENT_DTYPE, MS_STATE_DTYPE, clean_multiscale,
                   convolve_separable, ms_clean, ms_prepare, ms_scale_taps,
                   ms_weights)
-from ._lib import (LIB_PATH, BeamStruct, CleanParamsStruct, MsParamsStruct,
+from ._lib import (LIB_PATH, BeamStruct, ClarkParamsStruct,
+                   CleanParamsStruct, MsParamsStruct,
                    OptionsStruct, PlanParamsStruct, RestoreParamsStruct,
                    WeightParamsStruct)
 from . import shard
@@ -48,6 +50,7 @@ __all__ = [
     "WeightParamsStruct",
     "CLEAN_REASONS", "COMPONENT_DTYPE", "STATE_DTYPE", "clean", "model_image",
     "stokes_i", "CleanParamsStruct",
+    "CLARK_REASONS", "CLARK_STATE_DTYPE", "clark", "ClarkParamsStruct",
     "Beam", "beam_fit", "beam_from_axes", "beam_radius", "beam_taps",
     "restore", "BeamStruct", "RestoreParamsStruct",
     "MS_COMPONENT_DTYPE", "MS_STATE_DTYPE", "clean_multiscale",

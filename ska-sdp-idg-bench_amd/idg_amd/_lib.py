@@ -84,6 +84,8 @@ SIGNATURES = {
                                      _P, _P, _P, _P]),
     "idg_clean": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "idg_clean_launch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "idg_clark": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "idg_clark_launch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "idg_beam_from_axes": (_I, [_D, _D, _D, _P]),
     "idg_beam_fit": (_I, [_I, _P, _F, _P]),
     "idg_beam_radius": (_I, [_P, _D]),
@@ -142,6 +144,21 @@ class CleanParamsStruct(ctypes.Structure):
                 ("gain", ctypes.c_float),
                 ("threshold", ctypes.c_float),
                 ("cycle_fraction", ctypes.c_float)]
+
+
+class ClarkParamsStruct(ctypes.Structure):
+    """idg_clark_params_t (include/idg_mi355x.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint32),
+                ("grid_size", ctypes.c_int32),
+                ("psf_size", ctypes.c_int32),
+                ("max_components", ctypes.c_int32),
+                ("nr_rounds", ctypes.c_int32),
+                ("iterations_per_round", ctypes.c_int32),
+                ("max_candidates", ctypes.c_int32),
+                ("gain", ctypes.c_float),
+                ("threshold", ctypes.c_float),
+                ("cycle_fraction", ctypes.c_float),
+                ("select_fraction", ctypes.c_float)]
 
 
 class MsParamsStruct(ctypes.Structure):

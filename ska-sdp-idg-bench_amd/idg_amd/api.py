@@ -18,7 +18,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (BeamStruct, CleanParamsStruct, MsParamsStruct,
+from ._lib import (BeamStruct, ClarkParamsStruct, CleanParamsStruct,
+                   MsParamsStruct,
                    OptionsStruct, PlanParamsStruct, RestoreParamsStruct,
                    WeightParamsStruct, lib)
 
@@ -1247,6 +1248,78 @@ def clean(residual, psf,model=None, mask=None, gain=0.1, threshold=0.0,
         [(residual, "residual", True), (psf, "psf", False)], G,
         (COMPONENT_DTYPE, STATE_DTYPE), model, mask, max_components,
         nr_iterations, components, state, check_every, stream)
+    return residual, model, components, state
+
+
+# ---------------------------------------------------------------------------
+# Clark CLEAN (idg_clark / idg_clark_launch; not in the
+# reference): clean()'s minor cycle on a list of the brightest pixels, many
+# components per launch.  numpy arrays take the host entry, torch CUDA tensors
+# the _launch entry (asynchronous); the same bytes either way.
+#   ... -> clark(residual, psf) -> model_image -> predict
+# ---------------------------------------------------------------------------
+CLARK_STATE_DTYPE = np.dtype(STATE_DTYPE.descr + [
+    ("n_candidates", "<i4"), ("round_limit", "<f4"), ("rounds", "<i4")])
+assert CLARK_STATE_DTYPE.itemsize == 36
+CLARK_REASONS = {**CLEAN_REASONS, 4: "no_candidate"}
+
+
+def _clark_params(G, Gp, max_components, nr_rounds, iterations_per_round,
+                  max_candidates, gain, threshold, cycle_fraction,
+                  select_fraction):
+    p = ClarkParamsStruct()
+    p.struct_size = ctypes.sizeof(ClarkParamsStruct)
+    p.grid_size, p.psf_size = G, Gp
+    p.max_components, p.nr_rounds = max_components, nr_rounds
+    p.iterations_per_round = iterations_per_round
+    p.max_candidates = max_candidates
+    p.gain, p.threshold, p.cycle_fraction = gain, threshold, cycle_fraction
+    p.select_fraction = select_fraction
+    return p, ctypes.cast(ctypes.pointer(p), ctypes.c_void_p)
+
+
+def clark(residual, psf, model=None, mask=None, gain=0.1, threshold=0.0,
+          cycle_fraction=0.0, select_fraction=0.3, max_candidates=4096,
+          iterations_per_round=1000, max_components=1000, nr_rounds=None,
+          components=None, state=None, check_every=None, stream=None):
+    """Clark CLEAN (idg_clark / idg_clark_launch): nr_rounds rounds, each of
+    which lists the pixels of `residual` above max(level, select_fraction *
+    the peak) -- at most max_candidates of them, the limit raised to a
+    histogram bin's edge where more would qualify --, runs clean()'s minor
+    cycle on that list for up to iterations_per_round components and then
+    subtracts those components from the whole residual.  On the device a
+    round is five launches however many components it takes.  It stops as
+    clean() does, or with reason 4 when a round's list is empty.
+    residual, psf, mask, model, components, gain, threshold, cycle_fraction
+    and max_components: as for clean().  state: None for a fresh one, or that
+    of an earlier call to continue it: k calls of n rounds give the bytes of
+    one call of k * n.  numpy: CLARK_STATE_DTYPE [1]; torch: the same bytes as
+    int32 [9].  nr_rounds = None: rounds until state.reason is set, at most
+    max_components + 1 (iterations_per_round must then be at least 1, so that
+    a round takes a component or sets a reason); on the device that takes
+    check_every, which then defaults to 1.  check_every = n (device only): n
+    rounds are enqueued at a time and the 4 bytes of state.reason read back
+    between the chunks; None reads nothing back.  Returns (residual, model,
+    components, state)."""
+    G, Gp = _square(residual, "residual"), _square(psf, "psf")
+    if nr_rounds is None:
+        if iterations_per_round < 1:
+            raise ValueError("nr_rounds=None needs iterations_per_round >= 1")
+        # a round takes a component or sets a reason: these rounds suffice,
+        # and the loop ends on a state the launch form runs no round from
+        nr_rounds = max_components + 1
+        if check_every is None and not isinstance(residual, np.ndarray):
+            check_every = 1
+
+    def params(n):
+        return _clark_params(G, Gp, max_components, n, iterations_per_round,
+                             max_candidates, gain, threshold, cycle_fraction,
+                             select_fraction)
+    model, components, state = _minor_cycle(
+        "clark", (lib.idg_clark, lib.idg_clark_launch), params,
+        [(residual, "residual", True), (psf, "psf", False)], G,
+        (COMPONENT_DTYPE, CLARK_STATE_DTYPE), model, mask, max_components,
+        nr_rounds, components, state, check_every, stream)
     return residual, model, components, state
 
 
